@@ -6,7 +6,9 @@ VALU int32 peak.  One "step" = one full search of config 2 -- msg "bradfitz" (on
 SHA block), 2^32 nonces -- per GPU, i.e. gpuhash_min over the rank's shard plus the
 16-byte cross-rank merge.  Weak scaling: rank r searches [r*2^32, (r+1)*2^32).
 
-  python bench.py                       # N=1, defaults finish in well under a minute
+  python bench.py                       # N=1: set up, warm up, time K steps, print the line
+  python bench.py --full                # ... plus everything listed under "--full" below
+  python bench.py --dump-outputs DIR    # ... and write the last timed step's result to DIR
   python bench.py --gpus N              # ONE process drives devices 0..N-1 (the north_star
                                         # design: cost-balanced shards, a host thread +
                                         # stream per device, 16-byte host argmin); exits
@@ -18,13 +20,24 @@ SHA block), 2^32 nonces -- per GPU, i.e. gpuhash_min over the rank's shard plus 
 
 Inputs are resident on the device before timing (the message is a kernel argument;
 the nonce space is generated in registers), so value = whole-job nonces / max-over-
-ranks wall time of K steps.  Extra keys: roofline (dominant scan kernel, HIP-event
-timed in this run on the library's own stream), cpu_baseline (oracle/ C restatement
-of the reference loop, timed on this host on a bounded sample, rank 0 at N=1 only), and
-search_2p40: after the timed steps, ONE search of 'bradfitz' over [0, 2^40) on the same
+ranks wall time of K steps.  Extra key of every run: roofline (dominant scan kernel,
+HIP-event timed during the timed steps on the library's own stream; no run of its own).
+
+A plain run does nothing beyond the timed steps.  --full adds, after them: result_check
+(the timed step's (hash, nonce) against the committed CPU golden) and device_check (each
+shard ran on its device), both exit 3 on a miss; cpu_baseline (oracle/ C restatement
+of the reference loop, timed on this host on a bounded sample, rank 0 at N=1 only); and
+search_2p40: ONE search of 'bradfitz' over [0, 2^40) on the same
 N devices (north_star: "near-linear 1->8 GPU GH/s scaling on a 2^40-nonce search"), its
 time, GH/s, per-shard device ordinals, and its (hash, nonce) checked against the CPU
 golden (exit 3 on a mismatch).  ~33 s on one GPU, ~33/N s on N; --no-search skips it.
+--no-cpu-baseline, --cpu-seconds, --search and --no-search shape a --full run only.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, the merged
+(hash, nonce), as DIR/result.npy: float64, shape (2, 2), row 0 the hash and row 1 the
+nonce, each as its (high, low) 32-bit words, so both u64 values are exact.  The message
+and the nonce windows are fixed, so two builds given the same arguments are comparable
+word for word.
 """
 from __future__ import annotations
 
@@ -252,6 +265,16 @@ def emit(out: dict) -> None:
         sys.stdout.flush()
     else:
         os.write(_JSON_FD, line)
+
+
+def dump_outputs(path: str, res) -> None:
+    """--dump-outputs: the last timed step's merged (hash, nonce) as DIR/result.npy, float64
+    of shape (2, 2): [[hash >> 32, hash & 0xffffffff], [nonce >> 32, nonce & 0xffffffff]].
+    32-bit words are exact in float64; the u64 values themselves would not be."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    words = [[int(v) >> 32, int(v) & 0xFFFFFFFF] for v in res]
+    np.save(os.path.join(path, "result.npy"), np.array(words, dtype=np.float64))
 
 
 def dominant(recs: list[dict]) -> tuple[tuple, dict]:
@@ -606,7 +629,7 @@ def search_exit(out: dict, problems: list[str]) -> None:
 
 
 def add_cpu_baselines(out: dict, args) -> None:
-    if not args.no_cpu_baseline and args.config == "2":
+    if args.full and not args.no_cpu_baseline and args.config == "2":
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         out["cpu_baseline_multicore"] = cpu_baseline_multicore(args.cpu_seconds / 2)
         out["cpu_baseline_plain_c"] = cpu_baseline_plain_c(args.cpu_seconds / 4)
@@ -665,13 +688,16 @@ def main_inproc(args, devs: list[int]) -> None:
                     nonces_per_step=total_per_step, ranges=[list(w) for w in merged], devices=devs)
     out["per_device"], slow, slow_recs = per_device(recs, args.steps)
     out["result"] = list(res)
-    out["result_check"] = step_check(msg, merged, res)
-    out["matches_golden"] = out["result_check"]["matches_golden"]
+    if args.full:
+        out["result_check"] = step_check(msg, merged, res)
+        out["matches_golden"] = out["result_check"]["matches_golden"]
     out["launches_per_step"] = len(recs) // max(args.steps, 1)
     out["roofline"] = roofline(args.config, slow_recs)
     out["roofline"]["device"] = slow
     out["shards"] = shard_rows(recs)  # device evidence of the timed steps (kernel_ms over all K)
-    problems = check_shards(out["shards"], devs)
+    problems = check_shards(out["shards"], devs) if args.full else []
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     if args.search is not None:
         lo, hi = args.search
         barrier()
@@ -766,7 +792,7 @@ def main_ranks(args, world: int, rank: int, local: int) -> None:
     roof = roofline(args.config, recs)
     # device evidence of every rank: its shard of the timed steps ran on LOCAL_RANK's device
     mine = shard_rows(recs)
-    problems = check_shards(mine, [local])
+    problems = check_shards(mine, [local]) if args.full else []
     search = None
     if args.search is not None:
         from gpuhash.dist import split_range
@@ -847,9 +873,12 @@ def main_ranks(args, world: int, rank: int, local: int) -> None:
         out = base_line(args, value, world, dt, cfg["desc"], msg, f"dp{world}", "weak",
                         nonces_per_gpu=per_gpu, processes=world, backend=backend)
         out["result"] = list(res)  # (hash, nonce) argmin over every rank's windows
-        out["result_check"] = step_check(msg, merge_windows(w for r in range(world) for w in cfg["windows"](r)), res)
-        out["matches_golden"] = out["result_check"]["matches_golden"]
+        if args.full:
+            out["result_check"] = step_check(msg, merge_windows(w for r in range(world) for w in cfg["windows"](r)), res)
+            out["matches_golden"] = out["result_check"]["matches_golden"]
         out["roofline"] = roof
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
         problems = [f"rank {g['rank']}: {p}" for g in gathered for p in g["problems"]]
         out["rank_devices"] = [{"rank": g["rank"], "device": g["local_rank"], "pci": g["pci"], "host": g["host"]}
                                for g in gathered]
@@ -857,7 +886,7 @@ def main_ranks(args, world: int, rank: int, local: int) -> None:
         # pinned to one visible GPU each all report ordinal 0, and ordinals repeat across the
         # nodes of a multi-node launch
         gpus = [(g["host"], g["pci"]) for g in gathered]
-        if not shared and None not in (g["pci"] for g in gathered) and len(set(gpus)) != world:
+        if args.full and not shared and None not in (g["pci"] for g in gathered) and len(set(gpus)) != world:
             problems.append("ranks on distinct GPUs expected but two ranks share a (host, PCI) device")
         if search is not None:
             shards = [s for g in gathered for s in (g["search_shards"] or [])]
@@ -895,24 +924,35 @@ def main() -> None:
                          "through one gpuhash context")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else this script measures or "
+                         "checks: the timed step and the shards' devices against their goldens, "
+                         "the CPU baselines, the 2^40 search and its scaling re-run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's merged (hash, nonce) to DIR/result.npy "
+                         "(float64 (2, 2): rows hash, nonce; columns high, low 32-bit word)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--config", default="2", choices=sorted(CONFIGS))
     ap.add_argument("--inproc", default=None, metavar="DEVICES",
                     help="explicit device list for the one-process path (comma list, ordinals "
                          "may repeat to rehearse N shards on one GPU); overrides --gpus")
     ap.add_argument("--search", default="0:2^40-1", metavar="LO:HI|off",
-                    help="after the timed steps, one search of 'bradfitz' over [LO, HI] on the "
+                    help="with --full: after the timed steps, one search of 'bradfitz' over [LO, HI] on the "
                          "same devices, checked against the committed CPU golden of that range "
                          "(default: the north_star's 2^40-nonce search; 'off' skips it)")
-    ap.add_argument("--no-search", action="store_true", help="same as --search off")
+    ap.add_argument("--no-search", action="store_true", help="with --full: same as --search off")
     args = ap.parse_args()
     if args.gpus < 1:
         fail("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        fail("--steps must be >= 1 and --warmup >= 0")
     try:
         args.search = None if args.no_search else parse_search(args.search)
     except ValueError as e:
         fail(str(e))
+    if not args.full:  # the search leg belongs to --full
+        args.search = None
     _quiet_stdout()
     # torch before libgpuhash: both link libamdhip64, and the process must load torch's
     # HIP runtime first, or torch later finds "No HIP GPUs are available"

@@ -281,3 +281,21 @@ def test_alone_rerun_records_a_failure_instead_of_raising():
         raise RuntimeError("no device")
     s = bench.alone_rerun(boom, {"shard": 0, "device": 0, "windows": [[0, 9]]}, 1.0, lambda: None)
     assert s["error"] == "RuntimeError: no device" and "scaling_efficiency" not in s
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and r.stdout == ""
+
+
+def test_dump_outputs_keeps_every_bit(tmp_path):
+    """--dump-outputs: (hash, nonce) as (high, low) 32-bit words in float64, exact for any
+    u64 (the values themselves are not above 2^53); a second dump replaces the first."""
+    import numpy as np
+    d = tmp_path / "a" / "b"
+    for res in [(5256245051, 1626825724), ((1 << 64) - 1, (1 << 53) + 1), (0, 0)]:
+        bench.dump_outputs(str(d), res)
+        a = np.load(d / "result.npy")
+        assert a.dtype == np.float64 and a.shape == (2, 2)
+        assert tuple((int(hi) << 32) | int(lo) for hi, lo in a) == res
+    assert os.listdir(d) == ["result.npy"]

@@ -94,7 +94,8 @@ def _worker(rank, world, port, ndev, share, q, pinned=False):
     torch.cuda.synchronize = lambda d=None: None
     torch.cuda.get_device_properties = props
     args = types.SimpleNamespace(gpus=world, steps=2, warmup=1, no_cpu_baseline=True, cpu_seconds=1.0,
-                                 config="2", inproc=None, search=(0, 9999), no_search=False)
+                                 config="2", inproc=None, search=(0, 9999), no_search=False, full=True,
+                                 dump_outputs=None)
     out, err = io.StringIO(), io.StringIO()
     sys.stdout, sys.stderr = out, err
     code = 0

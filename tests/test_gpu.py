@@ -438,7 +438,8 @@ def test_distinct_devices_bench_inproc():
     n = gpuhash.device_count()
     if n < 2:
         pytest.skip(f"{n} HIP device visible: the distinct-device bench path needs >= 2")
-    p = _bench(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--search", "0:2^32-1"])
+    p = _bench(["--full", "--gpus", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--search",
+                "0:2^32-1"])
     out, err = p.communicate(timeout=300)
     assert p.returncode == 0, err[-2000:]
     line = json.loads(out.strip().splitlines()[-1])
@@ -463,8 +464,8 @@ def test_distinct_devices_bench_ranks_one_visible_gpu_each():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    procs = [_bench(["--gpus", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--search",
-                     "0:2^32-1"],
+    procs = [_bench(["--full", "--gpus", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                     "--search", "0:2^32-1"],
                     env=dict(RANK=str(r), LOCAL_RANK="0", WORLD_SIZE=str(n), LOCAL_WORLD_SIZE="1",
                              MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HIP_VISIBLE_DEVICES=str(r)))
              for r in range(n)]

@@ -89,7 +89,7 @@ def test_bench_inproc_two_shards_on_one_gpu(engine):
     """bench.py's in-process N=2 path rehearsed as two shards on the one GPU, INCLUDING the
     default search leg: config 4's whole [0, 2^40) of 'bradfitz' in one gpuhash_min over
     the two shards, checked by bench.py against the committed CPU golden."""
-    r = _bench(["--inproc", "0,0", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], timeout=240)
+    r = _bench(["--full", "--inproc", "0,0", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "inproc2"
@@ -132,7 +132,7 @@ def test_bench_torchrun_two_ranks_on_one_gpu(engine):
     port = _free_port()
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    r = _bench(["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
                 "--search", "0:4294967295"],
                {"GPUHASH_SHARE_GPU": "1"}, launcher=launcher)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -161,7 +161,7 @@ def test_bench_torchrun_two_ranks_on_one_gpu(engine):
     # same physical GPU (exit 3 after the line)
     import gpuhash
     if gpuhash.device_count() == 1:
-        r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+        r = _bench(["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
                     "--search", "0:4294967295"], launcher=launcher[:-1] + [str(_free_port())])
         assert r.returncode != 0
         assert "LOCAL_RANK 1" in r.stderr or "share a (host, PCI) device" in r.stderr, r.stderr[-1500:]
@@ -170,7 +170,7 @@ def test_bench_torchrun_two_ranks_on_one_gpu(engine):
 def test_bench_default_line_checks_its_step(engine):
     """The headline line at N = 1 (config 2, [0, 2^32)) compares its timed step's result with
     the committed golden and reports per-shard rates per step."""
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--search", "off"])
+    r = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--search", "off"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["matches_golden"] is True and line["result_check"]["golden_names"] == ["cfg2_bradfitz_2p32"]
@@ -178,3 +178,26 @@ def test_bench_default_line_checks_its_step(engine):
     assert sh["nonces"] == 1 << 32 and sh["nonces_hashed"] == 2 << 32
     assert sh["kernel_GHs"] == pytest.approx(line["per_device"][0]["kernel_GHs"], rel=1e-3)
     assert sh["kernel_GHs"] > 20 and 1500 < sh["sclk_mhz"] < 2600
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_result(engine, tmp_path):
+    """Without --full the run ends after its timed steps: no golden or device checks, no CPU
+    baselines, no search leg (whatever --search says).  --dump-outputs writes the last
+    step's (hash, nonce) as exact 32-bit words in float64."""
+    import numpy as np
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--search", "0:2^32-1",
+                "--dump-outputs", str(tmp_path / "dump")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("search_2p40", "cpu_baseline", "cpu_baseline_multicore", "cpu_baseline_plain_c",
+                "result_check", "matches_golden", "device_check"):
+        assert key not in line, key
+    assert line["unit"] == "GH/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["steps"] == 2 and line["shards"][0]["nonces_hashed"] == 2 << 32  # --steps is the step count
+    assert line["value"] == pytest.approx((1 << 32) / (line["ms_per_step"] * 1e-3) / 1e9, rel=1e-3)
+    assert line["roofline"]["kernel"] == "k_scan<J=4,C2=0,EX=0,MODE=0>"
+    assert tuple(line["result"]) == (5256245051, 1626825724)  # config 2's golden
+    assert os.listdir(tmp_path / "dump") == ["result.npy"]
+    a = np.load(tmp_path / "dump" / "result.npy")
+    assert a.dtype == np.float64 and a.shape == (2, 2)
+    assert [(int(hi) << 32) | int(lo) for hi, lo in a] == line["result"]

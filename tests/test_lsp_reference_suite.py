@@ -7,7 +7,8 @@ drop pattern and assertions, and drives `bitcoin-miner_amd/lsp` through the same
 (NewServer/NewClient/Read/Write/CloseConn/Close and the lspnet drop knobs of staff.go).
 
 Time is scaled. Tests that need epochs to pass run with EpochMillis / EPOCH_DIV (the
-500-message lsp4 tests: / EPOCH_DIV_BULK), floored at MIN_EPOCH_MS, and their time limits
+500-message lsp4 tests: / EPOCH_DIV_BULK, the other lsp4 tests: / EPOCH_DIV_SYNC), floored
+at MIN_EPOCH_MS, and their time limits
 (maxEpochs x EpochMillis) scale with it. Tests that
 must finish WITHOUT any epoch (TestBasic*, TestSendReceive*) keep their full epochs and
 time limits, so a message that needed a resend would still fail them.
@@ -43,6 +44,14 @@ MIN_EPOCH_MS = 100
 # (a 2 s window) they failed about half the time; they keep the Go test's full epochs
 # (the 4 s window).  The window tests use the same epochs (lsp2_test: 5 epochs of 0.5 s).
 EPOCH_DIV_BULK = 1
+
+
+# The 10-message lsp4 tests must move their buffered messages (10 window-1 round trips per
+# client, the first only at the next epoch's resend) while the network is on for 2 epochs.
+# At EPOCH_DIV's 100 ms epochs that leaves the Python threads about 100 ms, which a busy
+# host does not always grant; at 250 ms epochs the scenario, its epoch counts and its
+# assertions are the same and the window is 2.5x as long.
+EPOCH_DIV_SYNC = 2
 
 
 # Every scenario runs twice: with each datagram sent once (the protocol exactly as
@@ -748,7 +757,7 @@ class SyncSystem:
 def test_lsp4_sync(name, nc, nmsgs, mode, params, max_epochs):
     # "fastclose" moves data both ways like RoundTrip, but issues the server's Close while
     # the network is still off (lsp4_test.go:395-397)
-    div = EPOCH_DIV_BULK if nmsgs >= 500 else EPOCH_DIV
+    div = EPOCH_DIV_BULK if nmsgs >= 500 else EPOCH_DIV_SYNC
     if nmsgs >= 500 and SEND_COPIES > 1:
         # 5 x 500 window-1 round trips must fit the 2 epochs the network is on; with three
         # copies a Python endpoint sends and reads ~4x the datagrams per message, so under a

@@ -52,17 +52,19 @@ class Procs:
     def __init__(self):
         self.ps = []
 
-    def start(self, argv, cpu=None, **env):
-        """`cpu`: pin the process (every thread it will start) to that one CPU from exec on."""
+    def start(self, argv, cpu=None, stderr=subprocess.PIPE, **env):
+        """`cpu`: pin the process (every thread it will start) to that one CPU from exec on.
+        `stderr`: an open file instead of the pipe, for a log that is read while it grows."""
         e = dict(os.environ, **LSP, **{k: str(v) for k, v in env.items()})
         pin = None if cpu is None else (lambda: os.sched_setaffinity(0, {cpu}))
-        p = subprocess.Popen(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=e,
+        p = subprocess.Popen(argv, stdout=subprocess.PIPE, stderr=stderr, text=True, env=e,
                              preexec_fn=pin)
         self.ps.append(p)
         return p
 
-    def py(self, prog, *args, cpu=None, **env):
-        return self.start([sys.executable, os.path.join(BIN, prog), *map(str, args)], cpu=cpu, **env)
+    def py(self, prog, *args, cpu=None, stderr=subprocess.PIPE, **env):
+        return self.start([sys.executable, os.path.join(BIN, prog), *map(str, args)], cpu=cpu, stderr=stderr,
+                          **env)
 
     def stop(self, p):
         if p.poll() is None:
@@ -101,7 +103,11 @@ def test_config5_shape_under_cpu_pressure(procs, tmp_path, oracle):
     miner = build_miner(tmp_path)
     port = free_port()
     cpu = sorted(os.sched_getaffinity(0))[-1]
-    server = procs.py("server", port, cpu=cpu, GPUHASH_SERVER_LOG=1, GPUHASH_JOB_SIZE=1 << 21, **DROPS)
+    # the server's stderr goes to a file: the test reads it while the server runs
+    log_path = tmp_path / "server.log"
+    with open(log_path, "w") as log_file:
+        server = procs.py("server", port, cpu=cpu, stderr=log_file, GPUHASH_SERVER_LOG=1,
+                          GPUHASH_JOB_SIZE=1 << 21, **DROPS)
     hogs = _hogs(cpu, 8)
     try:
         time.sleep(0.5)
@@ -117,12 +123,19 @@ def test_config5_shape_under_cpu_pressure(procs, tmp_path, oracle):
         n = 1 << 22
         clients = [procs.py("client", f"127.0.0.1:{port}", f"client-{i:02d}", n, **DROPS) for i in range(8)]
         res = [c.communicate(timeout=240) for c in clients]
+        # the LSP loop reports its lateness once per 5-s window: on a host that serves the
+        # clients sooner than that, the server stays on the contended CPU until the first report
+        deadline = time.monotonic() + 30
+        while "window max lateness" not in log_path.read_text() and time.monotonic() < deadline:
+            assert server.poll() is None, log_path.read_text()[-1500:]
+            time.sleep(0.1)
         cg = sampler.stop()
     finally:
         for h in hogs:
             h.kill()
             h.wait()
-    log = procs.stop(server)
+    procs.stop(server)
+    log = log_path.read_text()
     merr = [procs.stop(m) for m in miners]
     late = sysdiag.lsp_lateness({"server": log, **{f"client-{i}": e for i, (_, e) in enumerate(res)},
                                  **{f"miner-{k}": e for k, e in enumerate(merr)}})

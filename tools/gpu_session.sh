@@ -53,13 +53,13 @@ for step in "$@"; do
         benchwait) for i in 1 2; do for m in stream poll; do
                        run benchwait_${m}_$i 200 env GPUHASH_HOST_WAIT=$m python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --search off
                    done; done ;;
-        bench) run bench 300 python -u bench.py --steps 10 --warmup 2 ;;
-        inproc8s) run inproc8s 300 python -u bench.py --inproc 0,0,0,0,0,0,0,0 --steps 2 --warmup 1 --no-cpu-baseline ;;
-        dist8s) run dist8s 400 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29549 bench.py --gpus 8 --steps 1 --warmup 1 ;;
-        inproc40) run inproc40 300 python -u bench.py --inproc 0,0 --steps 2 --warmup 1 --no-cpu-baseline ;;
-        nccl1) run nccl1 300 env GPUHASH_FORCE_DIST=1 GPUHASH_DIST_BACKEND=nccl python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline ;;
-        dist2) run dist2 300 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 ;;
-        inproc) run inproc2 300 python -u bench.py --inproc 0,0 --steps 3 --warmup 1 --no-cpu-baseline ;;
+        bench) run bench 300 python -u bench.py --full --steps 10 --warmup 2 ;;
+        inproc8s) run inproc8s 300 python -u bench.py --full --inproc 0,0,0,0,0,0,0,0 --steps 2 --warmup 1 --no-cpu-baseline ;;
+        dist8s) run dist8s 400 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29549 bench.py --full --gpus 8 --steps 1 --warmup 1 ;;
+        inproc40) run inproc40 300 python -u bench.py --full --inproc 0,0 --steps 2 --warmup 1 --no-cpu-baseline ;;
+        nccl1) run nccl1 300 env GPUHASH_FORCE_DIST=1 GPUHASH_DIST_BACKEND=nccl python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline ;;
+        dist2) run dist2 300 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 3 --warmup 1 ;;
+        inproc) run inproc2 300 python -u bench.py --full --inproc 0,0 --steps 3 --warmup 1 --no-cpu-baseline ;;
         latency) run latency 120 python -u tools/latency.py ;;
         ranks) run ranks 300 python -u tools/rank_windows.py --ranks "${RANKS:-0,1,2,3,4,5,6,7}" ;;
         sweep) run sweep 600 python -u tools/layout_sweep.py ;;
@@ -77,12 +77,12 @@ for step in "$@"; do
                 cp "$OUT/family.log" "$OUT/fam.jsonl"
                 run family_pmc 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/fam_pmc" -o pmc --output-format csv -- python3 tools/family_issue.py --once
                 run family_sum 60 python3 tools/family_issue.py --summarize "$OUT/fam_pmc" "$OUT/fam.jsonl" ;;
-        inproc8c4) run inproc8c4 300 python -u bench.py --inproc 0,0,0,0,0,0,0,0 --config 4 --steps 1 --warmup 1 --no-cpu-baseline ;;
+        inproc8c4) run inproc8c4 300 python -u bench.py --full --inproc 0,0,0,0,0,0,0,0 --config 4 --steps 1 --warmup 1 --no-cpu-baseline ;;
         soak) run soak $(( ${SOAK_SECONDS:-90} + 60 )) python -u tools/soak.py "${SOAK_SECONDS:-90}" "${SOAK_SEED:-2026}" ;;
         c4full) run c4full 400 python -u tools/config4_full.py ;;
-        dist8c4) run dist8c4 400 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29547 bench.py --gpus 8 --config 4 --steps 1 --warmup 0 ;;
-        bench3) run bench3 300 python -u bench.py --config 3 --steps 5 --warmup 1 ;;
-        bench4) run bench4 300 python -u bench.py --config 4 --steps 2 --warmup 1 ;;
+        dist8c4) run dist8c4 400 env GPUHASH_SHARE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29547 bench.py --full --gpus 8 --config 4 --steps 1 --warmup 0 ;;
+        bench3) run bench3 300 python -u bench.py --full --config 3 --steps 5 --warmup 1 ;;
+        bench4) run bench4 300 python -u bench.py --full --config 4 --steps 2 --warmup 1 ;;
         prof4) run prof_c4 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c4" -o bench --output-format csv -- python3 bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --no-search ;;
         prof) run prof 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-search ;;
         pmc) run pmc_valu 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/pmc1" -o pmc --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-search
