@@ -41,6 +41,7 @@ struct Dev {
     unsigned int* d_ncand = nullptr;
     Cand* d_best = nullptr;
     Cand* h_best = nullptr;  // pinned
+    unsigned int* h_nhit = nullptr;  // pinned: first-hit mode's candidate count (0 = no hit)
     uint32_t cap = 0;
     // launch descriptors + prefix offsets + per-launch work counters, staged through a
     // pinned host buffer and copied once per call
@@ -59,6 +60,7 @@ struct Dev {
     // per-call results
     int rc = GPUHASH_OK;
     uint64_t best_h = ~0ull, best_n = ~0ull;
+    bool found = false;  // first-hit mode: (best_h, best_n) is a hit
     bool used = false;
     double kernel_ms = 0;
     uint32_t launches = 0;
@@ -153,6 +155,7 @@ static int dev_init(Dev& d, int ord, int shard) {
     if (hipMalloc(&d.d_ncand, sizeof(unsigned int)) != hipSuccess) return GPUHASH_ENOMEM;
     if (hipMalloc(&d.d_best, sizeof(Cand)) != hipSuccess) return GPUHASH_ENOMEM;
     if (hipHostMalloc(&d.h_best, sizeof(Cand), hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
+    if (hipHostMalloc(&d.h_nhit, sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
     HIPCHK(hipMemset(d.d_ncand, 0, sizeof(unsigned int)));
     return GPUHASH_OK;
 }
@@ -170,6 +173,7 @@ static void dev_free(Dev& d) {
     if (d.d_best) hipFree(d.d_best);
     if (d.d_cands) hipFree(d.d_cands);
     if (d.h_best) hipHostFree(d.h_best);
+    if (d.h_nhit) hipHostFree(d.h_nhit);
     if (d.d_meta) hipFree(d.d_meta);
     if (d.d_ktab) hipFree(d.d_ktab);
     if (d.h_clk) hipHostFree(d.h_clk);
@@ -232,10 +236,16 @@ static int dev_reserve(Dev& d, uint32_t cap, size_t nev) {
 // Runs one device's shard.  The planned launches are grouped by kernel variant; each
 // group is ONE persistent launch over all its descriptors (guided self-scheduling, see
 // scan_kernel.h), followed by the candidate reduce.  One 16-byte copy back at the end.
-// mode 1 writes per-nonce hashes to d_dump instead.
+// mode 1 writes per-nonce hashes to d_dump instead.  mode 2 is the first-hit search
+// (gpuhash_first_below): d_thresh is the shared bound, the lowest qualifying nonce found so
+// far, `target` travels in the kernels' dump_lo argument, the workgroups append only real
+// hits (nonce and hash swapped, so the same reduce picks the lowest nonce), and the append
+// counter, copied back before the reduce resets it, is the found flag.
 static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
-                   uint32_t rchunk, int mode, unsigned long long* d_dump, int policy) {
+                   uint32_t rchunk, int mode, unsigned long long* d_dump, int policy,
+                   uint64_t target = 0) {
     d.used = true;
+    d.found = false;
     d.kernel_ms = 0;
     d.launches = 0;
     d.recs.clear();
@@ -361,14 +371,16 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
         a.cands = d.d_cands;
         a.ncand = d.d_ncand;
         a.dump = d_dump;
-        a.dump_lo = lo;
+        a.dump_lo = mode == 2 ? target : lo;
         a.ktab = groups[g].C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + ptab_at[g]) : d.d_ktab;
         a.grid = grids[g];
         HIPCHK(hipEventRecord(d.ev[2 * g], a.stream));
         HIPCHK(launch_scan(groups[g].J, groups[g].C2, groups[g].EX, mode, a));
         HIPCHK(hipEventRecord(d.ev[2 * g + 1], a.stream));
     }
-    if (mode == 0) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
+    if (mode == 2)
+        HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_ncand, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
+    if (mode != 1) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
     HIPCHK(hipMemcpyAsync(d.h_best, d.d_best, sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * groups.size(), hipMemcpyDeviceToHost, d.stream));
     if ((rc = host_wait(d))) return rc;
@@ -394,6 +406,11 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
     d.launches = (uint32_t)groups.size();
     d.best_h = d.h_best->hash;
     d.best_n = d.h_best->nonce;
+    if (mode == 2) {  // stored swapped
+        d.found = *d.h_nhit > 0;
+        d.best_h = d.h_best->nonce;
+        d.best_n = d.h_best->hash;
+    }
     return GPUHASH_OK;
 }
 
@@ -500,14 +517,16 @@ int gpuhash_set_layout_policy(gpuhash_ctx* ctx, int policy) {
 
 // One slice of a search: sharded over the context's devices, each shard on its own
 // host thread + stream, 16-byte host argmin.  Accumulates into st / ctx->recs.
+// mode 2 (first hit): `any` says a hit exists, and the lowest-nonce hit of the shards wins.
 static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
                      uint64_t upper, uint32_t rchunk, uint64_t& bh, uint64_t& bn, bool& any,
-                     gpuhash_stats& st) {
+                     gpuhash_stats& st, int mode = 0, uint64_t target = 0) {
     const int n = (int)ctx->devs.size();
     std::vector<Shard> sh = shard_range(msg_len, lower, upper, n, ctx->policy);
     for (auto& d : ctx->devs) { d.used = false; d.rc = GPUHASH_OK; d.kernel_ms = 0; d.launches = 0; }
     if (n == 1) {
-        ctx->devs[0].rc = dev_run(ctx->devs[0], msg, msg_len, lower, upper, rchunk, 0, nullptr, ctx->policy);
+        ctx->devs[0].rc = dev_run(ctx->devs[0], msg, msg_len, lower, upper, rchunk, mode, nullptr, ctx->policy,
+                                  target);
     } else {
         std::vector<std::thread> th;
         th.reserve((size_t)n);
@@ -520,8 +539,8 @@ static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint6
             th.emplace_back([&, i] {
                 Dev& d = ctx->devs[(size_t)i];
                 try {
-                    d.rc = dev_run(d, msg, msg_len, sh[(size_t)i].lo, sh[(size_t)i].hi, rchunk, 0, nullptr,
-                                   ctx->policy);
+                    d.rc = dev_run(d, msg, msg_len, sh[(size_t)i].lo, sh[(size_t)i].hi, rchunk, mode, nullptr,
+                                   ctx->policy, target);
                 } catch (const std::bad_alloc&) {
                     d.used = true;
                     d.rc = GPUHASH_ENOMEM;
@@ -543,8 +562,12 @@ static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint6
         if (!d.used) continue;
         if (d.rc) return d.rc;
         // host argmin over the per-device 16-byte results
-        if (!any || d.best_h < bh || (d.best_h == bh && d.best_n < bn)) { bh = d.best_h; bn = d.best_n; }
-        any = true;
+        if (mode == 2) {
+            if (d.found && (!any || d.best_n < bn)) { bh = d.best_h; bn = d.best_n; any = true; }
+        } else {
+            if (!any || d.best_h < bh || (d.best_h == bh && d.best_n < bn)) { bh = d.best_h; bn = d.best_n; }
+            any = true;
+        }
         ctx->recs.insert(ctx->recs.end(), d.recs.begin(), d.recs.end());
         st.launches += d.launches;
         st.kernel_ms += d.kernel_ms;
@@ -552,11 +575,11 @@ static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint6
     return GPUHASH_OK;
 }
 
-int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
-                   uint64_t upper, uint32_t rchunk, uint64_t* out_hash, uint64_t* out_nonce) {
-    if (!ctx || !out_hash || !out_nonce || (msg_len && !msg)) return GPUHASH_EINVAL;
-    if (lower > upper) return GPUHASH_EINVAL;
-    if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
+// The slice loop of gpuhash_min_ex (mode 0) and gpuhash_first_below_ex (mode 2, where
+// out_found is set and the loop stops after the first slice that has a hit).
+static int search(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper,
+                  uint32_t rchunk, int mode, uint64_t target, uint64_t* out_hash, uint64_t* out_nonce,
+                  int* out_found) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     try {
         auto t0 = std::chrono::steady_clock::now();
@@ -581,7 +604,7 @@ int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
         uint32_t ndev_used = 0;
         for (uint64_t lo = lower;;) {
             const uint64_t hi = upper - lo < slice ? upper : lo + (slice - 1);
-            int rc = run_slice(ctx, msg, msg_len, lo, hi, rchunk, bh, bn, any, st);
+            int rc = run_slice(ctx, msg, msg_len, lo, hi, rchunk, bh, bn, any, st, mode, target);
             if (rc) return rc;
             double slice_max = 0;
             uint32_t used = 0;
@@ -592,14 +615,19 @@ int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
             }
             st.max_dev_kernel_ms += slice_max;  // devices run a slice concurrently
             ndev_used = std::max(ndev_used, used);
-            if (hi == upper) break;
+            if (hi == upper || (mode == 2 && any)) break;
             lo = hi + 1;
         }
         st.ndevices = ndev_used;
-        uint64_t span = upper - lower;
+        // first hit: what an ascending scan would have examined
+        uint64_t span = (mode == 2 && any ? bn : upper) - lower;
         st.nonces = span == ~0ull ? ~0ull : span + 1;
         st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         ctx->last = st;
+        if (mode == 2) {
+            *out_found = any ? 1 : 0;
+            if (!any) return GPUHASH_OK;  // outputs untouched
+        }
         *out_hash = bh;
         *out_nonce = bn;
         return GPUHASH_OK;
@@ -608,6 +636,29 @@ int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
     } catch (...) {  // no C++ exception crosses the C ABI into a Go or Python host
         return GPUHASH_EHIP;
     }
+}
+
+int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
+                   uint64_t upper, uint32_t rchunk, uint64_t* out_hash, uint64_t* out_nonce) {
+    if (!ctx || !out_hash || !out_nonce || (msg_len && !msg)) return GPUHASH_EINVAL;
+    if (lower > upper) return GPUHASH_EINVAL;
+    if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
+    return search(ctx, msg, msg_len, lower, upper, rchunk, 0, 0, out_hash, out_nonce, nullptr);
+}
+
+int gpuhash_first_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
+                           uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t* out_hash,
+                           uint64_t* out_nonce, int* out_found) {
+    if (!ctx || !out_hash || !out_nonce || !out_found || (msg_len && !msg)) return GPUHASH_EINVAL;
+    if (lower > upper) return GPUHASH_EINVAL;
+    if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
+    return search(ctx, msg, msg_len, lower, upper, rchunk, 2, target, out_hash, out_nonce, out_found);
+}
+
+int gpuhash_first_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
+                        uint64_t upper, uint64_t target, uint64_t* out_hash, uint64_t* out_nonce,
+                        int* out_found) {
+    return gpuhash_first_below_ex(ctx, msg, msg_len, lower, upper, target, 0, out_hash, out_nonce, out_found);
 }
 
 int gpuhash_min(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -695,9 +746,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.3 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.4 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.3 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.4 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

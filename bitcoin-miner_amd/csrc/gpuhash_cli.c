@@ -8,6 +8,8 @@
  *
  *   gpuhash_cli MSG LOWER UPPER        -> "Result <hash> <nonce>" (the client's output format)
  *   gpuhash_cli --range MSG LOWER COUNT -> one hash per line (gpuhash_hash_range)
+ *   gpuhash_cli --below MSG LOWER UPPER TARGET -> "Result <hash> <nonce>" of the lowest nonce
+ *                                         whose hash is <= TARGET, or "None" (gpuhash_first_below)
  *   gpuhash_cli --version
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
  */
@@ -38,13 +40,17 @@ int main(int argc, char **argv) {
         return 0;
     }
     const int range_mode = argc == 5 && strcmp(argv[1], "--range") == 0;
-    if (!range_mode && argc != 4) {
-        fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --version\n", argv[0]);
+    const int below_mode = argc == 6 && strcmp(argv[1], "--below") == 0;
+    if (!range_mode && !below_mode && argc != 4) {
+        fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
+                        " | --version\n", argv[0]);
         return 2;
     }
-    const char *msg = argv[range_mode ? 2 : 1];
-    uint64_t a, b;
-    if (parse_u64(argv[range_mode ? 3 : 2], &a) || parse_u64(argv[range_mode ? 4 : 3], &b)) {
+    const int opt = range_mode || below_mode;
+    const char *msg = argv[opt ? 2 : 1];
+    uint64_t a, b, target = 0;
+    if (parse_u64(argv[opt ? 3 : 2], &a) || parse_u64(argv[opt ? 4 : 3], &b) ||
+        (below_mode && parse_u64(argv[5], &target))) {
         fprintf(stderr, "bad number\n");
         return 2;
     }
@@ -60,6 +66,20 @@ int main(int argc, char **argv) {
         if (rc) status = fail("gpuhash_hash_range", rc);
         for (uint64_t i = 0; !rc && i < b; i++) printf("%" PRIu64 "\n", out[i]);
         free(out);
+    } else if (below_mode) {
+        uint64_t h = 0, n = 0;
+        int found = 0;
+        rc = gpuhash_first_below(ctx, (const uint8_t *)msg, len, a, b, target, &h, &n, &found);
+        if (rc) {
+            status = fail("gpuhash_first_below", rc);
+        } else if (!found) {
+            printf("None\n");
+        } else if (gpuhash_hash_cpu((const uint8_t *)msg, len, n) != h || h > target) {
+            fprintf(stderr, "self-check failed: Hash(msg, %" PRIu64 ") != %" PRIu64 " or above the target\n", n, h);
+            status = 4;
+        } else {
+            printf("Result %" PRIu64 " %" PRIu64 "\n", h, n);
+        }
     } else {
         uint64_t h = 0, n = 0;
         rc = gpuhash_min(ctx, (const uint8_t *)msg, len, a, b, &h, &n);

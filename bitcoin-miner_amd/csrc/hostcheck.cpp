@@ -6,6 +6,7 @@
 // padding block).  tests/test_plan.py compares it against the oracle on CPU so that a
 // wrong host precomputation is caught without a GPU.  Not linked into libgpuhash.so
 // and never used to produce a search result.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -86,20 +87,14 @@ double gpuhash_plan_cost(const uint8_t* msg, uint64_t len, uint64_t lower, uint6
     return plan_cost(v);
 }
 
-// Replays the kernel's per-nonce computation from launch `idx`'s descriptor.
-int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
-                        uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
-    std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, rchunk, g_policy, /*host_ptab=*/true);
-    if (idx < 0 || idx >= (int)v.size()) return -1;
-    const Launch& l = v[(size_t)idx];
+}  // extern "C"
+
+// The data flow of one nonce of launch l, given as the kernel holds it: the lane value p
+// (C2 = 3: x) and the loop value r.
+static uint64_t replay_hash(const Launch& l, uint32_t p, uint32_t r) {
     const LaunchDesc& D = l.desc;
-    if (nonce < l.lo || nonce > l.hi) return -2;
     if (l.C2 == 3) {
-        // lane table: x = lane value (W_0/W_1 digits), r = loop value (p-table entry)
-        const uint64_t off = nonce - D.base;
-        const uint32_t r = (uint32_t)(off / D.RQ), x = (uint32_t)(off % D.RQ);
-        if (x < D.p_first || x > D.p_last || r >= D.R) return -3;  // not a rectangle
+        const uint32_t x = p;
         const uint32_t* P = &l.ptab[16ull * r];
         uint32_t W[64], st[8];
         std::memcpy(W, D.U, 64);
@@ -111,14 +106,8 @@ int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64
         const uint32_t kw0 = kK[0] + W[0];
         uint32_t s1[8] = {P[8] + P[9] + kw0, st[0], st[1], st[2], st[3] + P[8] + kw0, st[4], st[5], st[6]};
         sha256_rounds(s1, W, 1, 64);
-        *out = ((uint64_t)(P[0] + s1[0]) << 32) | (uint32_t)(P[1] + s1[1]);
-        return 0;
+        return ((uint64_t)(P[0] + s1[0]) << 32) | (uint32_t)(P[1] + s1[1]);
     }
-    // tail-digit launch: the kernel iterates k = nonce / stride; the tail digit is a
-    // constant byte of D.U
-    if (nonce % D.stride != D.tail) return -2;
-    const uint64_t off = nonce / D.stride - D.base;
-    const uint32_t p = (uint32_t)(off / D.R), r = (uint32_t)(off % D.R);
     const uint32_t alo = ascii4(p % 10000u), ahi = ascii4((p / 10000u) % 10000u);
     uint32_t W[64], st[8], cv[8];
     std::memcpy(W, D.U, 64);
@@ -166,8 +155,247 @@ int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64
         sha256_rounds(s2, kwx_minus_k, 0, 64);
         for (int i = 0; i < 8; i++) y[i] += s2[i];
     }
-    *out = ((uint64_t)y[0] << 32) | y[1];
+    return ((uint64_t)y[0] << 32) | y[1];
+}
+
+extern "C" {
+
+// Replays the kernel's per-nonce computation from launch `idx`'s descriptor.
+int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                        uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
+    std::vector<Launch> v;
+    plan_range(msg, len, lower, upper, v, rchunk, g_policy, /*host_ptab=*/true);
+    if (idx < 0 || idx >= (int)v.size()) return -1;
+    const Launch& l = v[(size_t)idx];
+    const LaunchDesc& D = l.desc;
+    if (nonce < l.lo || nonce > l.hi) return -2;
+    if (l.C2 == 3) {
+        // lane table: x = lane value (W_0/W_1 digits), r = loop value (p-table entry)
+        const uint64_t off = nonce - D.base;
+        const uint32_t r = (uint32_t)(off / D.RQ), x = (uint32_t)(off % D.RQ);
+        if (x < D.p_first || x > D.p_last || r >= D.R) return -3;  // not a rectangle
+        *out = replay_hash(l, x, r);
+        return 0;
+    }
+    // tail-digit launch: the kernel iterates k = nonce / stride; the tail digit is a
+    // constant byte of D.U
+    if (nonce % D.stride != D.tail) return -2;
+    const uint64_t off = nonce / D.stride - D.base;
+    *out = replay_hash(l, (uint32_t)(off / D.R), (uint32_t)(off % D.R));
     return 0;
+}
+
+}  // extern "C"
+
+// ---- first-hit search (gpuhash_first_below): CPU replay of the kernel's MODE 2 ----
+//
+// The same plan, variant groups, pieces, parts, masks, lower-bound function
+// (part_min_nonce, plan.h) and skip rule as k_scan<.., 2>, with the per-descriptor replay
+// above as the hash.  What a GPU decides by timing -- the order in which workgroups take
+// the pieces, and which of them read the shared bound before another publishes -- is
+// chosen here by a seed, so the tests can show the answer does not depend on it.
+
+namespace {
+
+// One part of a piece, as the kernel's inner loop cuts it: a row of one descriptor and the
+// loop values [r0, r1).
+struct Part {
+    const Launch* l;
+    uint32_t row, r0, r1;
+    uint64_t pos;   // position of (row, r0) in the group's row-iterations
+    uint64_t dend;  // end of the part's descriptor there (offs[i + 1])
+};
+
+// One variant group of a plan: its launches and their prefix offsets in row-iterations
+// (dev_run's `offs`), and the pieces the workgroups grab.
+struct VGroup {
+    std::vector<const Launch*> ls;
+    std::vector<uint64_t> offs;
+    std::vector<std::pair<uint64_t, uint64_t>> pieces;  // [x, end)
+};
+
+// Resident workgroups assumed for the grab sizes (8 per CU on 256 CUs; the real figure
+// comes from the occupancy query and only changes how the same work is cut).
+constexpr uint64_t kReplayGrid = 2048;
+
+std::vector<VGroup> group_plan(const std::vector<Launch>& plan, uint32_t rchunk) {
+    std::vector<VGroup> gs;
+    std::vector<const Launch*> firsts;
+    for (const Launch& l : plan) {
+        size_t g = 0;
+        while (g < gs.size() && !(firsts[g]->J == l.J && firsts[g]->C2 == l.C2 && firsts[g]->EX == l.EX)) g++;
+        if (g == gs.size()) { gs.emplace_back(); firsts.push_back(&l); }
+        gs[g].ls.push_back(&l);
+    }
+    const uint64_t gmax = rchunk ? rchunk : 400u, gmin = std::min<uint64_t>(10u, gmax);
+    for (VGroup& g : gs) {
+        uint64_t acc = 0;
+        for (const Launch* l : g.ls) {
+            g.offs.push_back(acc);
+            acc += (uint64_t)((l->desc.p_last - l->desc.p_first) / (uint32_t)kBlock + 1u) * l->desc.R;
+        }
+        g.offs.push_back(acc);
+        const uint64_t grid = std::min<uint64_t>(kReplayGrid, std::max<uint64_t>((acc + 9) / 10, 1));
+        // guided self-scheduling: piece = clamp(remaining / (2 * grid), gmin, gmax)
+        for (uint64_t cur = 0; cur < acc;) {
+            uint64_t p = (acc - cur) / (2 * grid);
+            p = p < gmin ? gmin : (p > gmax ? gmax : p);
+            g.pieces.push_back({cur, std::min(cur + p, acc)});
+            cur += p;
+        }
+    }
+    return gs;
+}
+
+void cut_parts(const VGroup& g, uint64_t x, uint64_t end, std::vector<Part>& out) {
+    const int ndesc = (int)g.ls.size();
+    while (x < end) {
+        int i = 0;
+        while (i + 1 < ndesc && g.offs[(size_t)i + 1] <= x) i++;
+        const LaunchDesc& D = g.ls[(size_t)i]->desc;
+        const uint32_t rel = (uint32_t)(x - g.offs[(size_t)i]);
+        const uint32_t row = rel / D.R, r0 = rel - row * D.R;
+        const uint64_t left = end - x;
+        const uint32_t r1 = (uint64_t)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
+        out.push_back(Part{g.ls[(size_t)i], row, r0, r1, x, g.offs[(size_t)i + 1]});
+        x += r1 - r0;
+    }
+}
+
+// Calls f(lane value, loop value, nonce) for every nonce the kernel's masks admit in a
+// part: lanes up to p_last, and r within [r_first, r_last] on the launch's first / last
+// lane value (scan_row's lane_ok, rlo, rhi; scan_row_lt has only lane_ok).
+template <class F>
+void for_each_nonce(const Part& pt, F&& f) {
+    const LaunchDesc& D = pt.l->desc;
+    for (uint32_t t = 0; t < (uint32_t)kBlock; t++) {
+        const uint64_t p64 = (uint64_t)D.p_first + (uint64_t)pt.row * 256u + t;
+        if (p64 > D.p_last) break;
+        const uint32_t p = (uint32_t)p64;
+        if (pt.l->C2 == 3) {
+            for (uint32_t r = pt.r0; r < pt.r1; r++) f(p, r, D.base + (uint64_t)r * D.RQ + p);
+            continue;
+        }
+        const uint32_t rlo = p == D.p_first ? D.r_first : 0u;
+        const uint32_t rhi = p == D.p_last ? D.r_last : D.R - 1u;
+        for (uint32_t r = std::max(pt.r0, rlo); r < pt.r1 && r <= rhi; r++)
+            f(p, r, (D.base + (uint64_t)p * D.R + r) * D.stride + D.tail);
+    }
+}
+
+struct Rng {  // splitmix64
+    uint64_t s;
+    uint64_t next() {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// The first-hit search of [lower, upper] as the kernels run it.  order_seed picks the order
+// in which each variant group's pieces are taken: 0 ascending, 1 strictly descending, any
+// other value a shuffle in which random batches of 1-8 pieces are "in flight" together,
+// i.e. all read the shared bound before any of them publishes a hit.  Returns 0 and
+// *found, (*hash, *nonce) (untouched when nothing qualifies), and in *pieces_skipped the
+// pieces whose every part the skip rule dropped unhashed.
+// The kernel's second step -- a skipped part of a descriptor other than a lane table's takes
+// the rest of that descriptor off the work counter (atomicMax) -- is replayed as a list of
+// cancelled position ranges.  On the GPU it only touches pieces not yet handed out, which
+// all lie further on; here it drops those positions from every piece visited later, in
+// whatever order, which skips more than the kernel can and so checks the rule harder.
+int hostcheck_first_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                          uint32_t rchunk, uint64_t target, uint64_t order_seed, uint64_t* hash,
+                          uint64_t* nonce, int* found, uint64_t* pieces_skipped) {
+    if (lower > upper || !hash || !nonce || !found || !pieces_skipped) return -1;
+    std::vector<Launch> plan;
+    plan_range(msg, len, lower, upper, plan, rchunk, g_policy, /*host_ptab=*/true);
+    const std::vector<VGroup> groups = group_plan(plan, rchunk);
+    uint64_t bound = ~0ull;  // the word `thresh` points to
+    bool any = false;
+    uint64_t best_n = 0, best_h = 0, skipped = 0;
+    Rng rng{order_seed};
+    for (const VGroup& g : groups) {  // the groups run back to back on one stream
+        std::vector<std::pair<uint64_t, uint64_t>> cancelled;  // [from, to) positions
+        auto is_cancelled = [&](uint64_t pos) {
+            for (const auto& c : cancelled)
+                if (pos >= c.first && pos < c.second) return true;
+            return false;
+        };
+        std::vector<size_t> order(g.pieces.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = i;
+        if (order_seed == 1) std::reverse(order.begin(), order.end());
+        else if (order_seed != 0)
+            for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
+        for (size_t at = 0; at < order.size();) {
+            const size_t batch = order_seed <= 1 ? 1 : std::min<size_t>(1 + rng.next() % 8, order.size() - at);
+            const uint64_t seen = bound;  // read once per grab, before the batch publishes
+            uint64_t publish = ~0ull;
+            bool hit = false;
+            for (size_t k = at; k < at + batch; k++) {
+                std::vector<Part> parts;
+                cut_parts(g, g.pieces[order[k]].first, g.pieces[order[k]].second, parts);
+                bool all_skipped = true;
+                for (const Part& pt : parts) {
+                    if (is_cancelled(pt.pos)) continue;
+                    if (part_min_nonce(pt.l->desc, pt.l->C2, pt.row, pt.r0) > seen) {
+                        if (pt.l->C2 != 3) cancelled.push_back({pt.pos, pt.dend});
+                        continue;
+                    }
+                    all_skipped = false;
+                    for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                        const uint64_t h = replay_hash(*pt.l, p, r);
+                        if (h > target) return;
+                        if (!any || n < best_n) { best_n = n; best_h = h; any = true; }
+                        if (!hit || n < publish) { publish = n; hit = true; }
+                    });
+                }
+                skipped += all_skipped ? 1 : 0;
+            }
+            if (hit && publish < bound) bound = publish;  // atomicMin
+            at += batch;
+        }
+    }
+    *found = any ? 1 : 0;
+    *pieces_skipped = skipped;
+    if (any) { *hash = best_h; *nonce = best_n; }
+    return 0;
+}
+
+// Every part of every piece of the plan of [lower, upper], for checking the lower-bound
+// function directly: bound[i] = part_min_nonce of part i, least[i] = the smallest nonce the
+// kernel's masks admit in it, count[i] = how many they admit (0: least[i] is unset).
+// Fills up to cap entries; returns the number of parts.
+int hostcheck_parts(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper, uint32_t rchunk,
+                    uint64_t* bound, uint64_t* least, uint64_t* count, int cap) {
+    if (lower > upper) return -1;
+    std::vector<Launch> plan;
+    plan_range(msg, len, lower, upper, plan, rchunk, g_policy);
+    int n = 0;
+    for (const VGroup& g : group_plan(plan, rchunk)) {
+        for (const auto& pc : g.pieces) {
+            std::vector<Part> parts;
+            cut_parts(g, pc.first, pc.second, parts);
+            for (const Part& pt : parts) {
+                if (n < cap) {
+                    uint64_t lo = 0, c = 0;
+                    for_each_nonce(pt, [&](uint32_t, uint32_t, uint64_t x) {
+                        if (!c || x < lo) lo = x;
+                        c++;
+                    });
+                    bound[n] = part_min_nonce(pt.l->desc, pt.l->C2, pt.row, pt.r0);
+                    least[n] = lo;
+                    count[n] = c;
+                }
+                n++;
+            }
+        }
+    }
+    return n;
 }
 
 }  // extern "C"

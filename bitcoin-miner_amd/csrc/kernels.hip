@@ -1,5 +1,6 @@
 // kernels.hip -- launch dispatch for the gfx950 scan kernels (instantiated in
-// kernels_{plain,ut,misc}.hip, see scan_decl.h) and the candidate reduce.
+// kernels_{plain,ut,misc}.hip, and their first-hit MODE 2 instances in
+// kernels_{plain,ut,misc}_first.hip; see scan_decl.h) and the candidate reduce.
 #include <atomic>
 
 #include "kernels.h"
@@ -130,12 +131,14 @@ struct Occupancy {
 
 unsigned int grid_for(int J, int C2, int EX, int mode, int device) {
     if (!valid_variant(J, C2, EX)) return 0;
+    if (mode == 2) return with_variant<2>(J, C2, EX, Occupancy{device});
     return mode == 0 ? with_variant<0>(J, C2, EX, Occupancy{device})
                      : with_variant<1>(J, C2, EX, Occupancy{device});
 }
 
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a) {
     if (!valid_variant(J, C2, EX) || a.grid == 0 || a.ndesc <= 0) return hipErrorInvalidValue;
+    if (mode == 2) return with_variant<2>(J, C2, EX, Launcher{a});
     return mode == 0 ? with_variant<0>(J, C2, EX, Launcher{a}) : with_variant<1>(J, C2, EX, Launcher{a});
 }
 

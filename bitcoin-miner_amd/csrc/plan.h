@@ -86,6 +86,31 @@ struct LaunchDesc {
     uint32_t pad2_;
 };
 
+#ifdef __HIPCC__
+#define GPUHASH_HD __host__ __device__
+#else
+#define GPUHASH_HD
+#endif
+
+// A lower bound of every nonce that the part (row, loop values r >= r0) of descriptor D
+// holds, for the first-hit search (gpuhash_first_below: the scan kernel's MODE 2 and its
+// CPU replay call this one function).  A row is 256 consecutive lane values from
+// p_first + 256 * row; the bound is the nonce of the row's first lane at r0:
+//   plain, C2 = 1, 2   (base + p * R + r0) * stride + tail   -- lanes and loop values both
+//                      raise the nonce, and a tail-digit launch's stride and tail apply to
+//                      every nonce of the descriptor alike
+//   C2 = 3             base + r0 * RQ + x                    -- the roles are swapped
+// The edge masks (r_first / r_last, lanes past p_last) only remove nonces, so the bound
+// holds with them.  All arithmetic is modulo 2^64: the exact value exceeds 2^64-1 only
+// when the part holds no nonce of the range at all (the row's first lane is then past the
+// launch's last nonce), and the wrapped value is merely a smaller bound.  It is never
+// above a nonce the part really holds.
+GPUHASH_HD inline uint64_t part_min_nonce(const LaunchDesc& D, int C2, uint32_t row, uint32_t r0) {
+    const uint64_t p = (uint64_t)D.p_first + (uint64_t)row * 256u;
+    if (C2 == 3) return D.base + (uint64_t)r0 * D.RQ + p;
+    return (D.base + p * D.R + r0) * D.stride + D.tail;
+}
+
 struct Launch {
     int J;          // loop word index in block B
     int C2;         // 1: lane block B-1 compressed per lane; 2: and W_0, W_1 are loop words

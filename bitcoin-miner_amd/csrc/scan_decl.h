@@ -6,6 +6,8 @@
 //   kernels_ut.hip     C2 = 1, J = 0 (K+W table layouts), C2 = 3 (lane table) + k_ktab:
 //                      max-ILP scheduling
 //   kernels_misc.hip   C2 = 1/J = 1, C2 = 2, extra-block layouts: max-ILP scheduling
+// The first-hit instances (MODE 2) of each family are in kernels_{plain,ut,misc}_first.hip,
+// built with that family's options.
 // kernels.hip launches them through these declarations only, so nothing is implicitly
 // instantiated there.
 #pragma once

@@ -21,6 +21,13 @@
 // the inclusive range with the lowest nonce winning ties (spec'd loop p1.pdf pp.12-14,
 // north_star).  The pruning is exact: T only ever holds the high word of a hash some
 // valid nonce already achieved, and ties on the high word take the slow path.
+//
+// MODE 2 is the other question, gpuhash_first_below: the LOWEST nonce whose hash is at or
+// below a target.  Per nonce it costs what MODE 0 costs (the same v_cmp and ballot, T = the
+// target's high word); the word `thresh` points to holds the lowest qualifying nonce found
+// so far, and parts of the work that lie wholly above it are skipped unhashed (k_scan, at
+// the grab).  Its instances live in kernels_*_first.hip; MODE 0 and MODE 1 compile to the
+// same machine code with or without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -161,6 +168,46 @@ struct WaveBest {
     uint32_t T;
 };
 
+// MODE 2 (first hit, gpuhash_first_below).  wb.T is the high word of the target, and the
+// rest of the mode's state lives in LDS, touched only by the rare slow path and at grabs:
+// the search kernels' SGPR budget is full (one more live pair spills), and this frees the
+// four that MODE 0 keeps its running best in.  A nonce of 2^64-1 is a legal hit, so
+// `found` says whether a wave has one; no nonce value stands for "none".
+struct FirstState {
+    unsigned long long target;
+    unsigned long long* bound;  // the word `thresh` points to: lowest qualifying nonce anywhere
+    unsigned long long grab_bound;  // that word as thread 0 read it at this grab: ONE value
+                                    // for the whole workgroup (see k_scan)
+    unsigned long long n[4], h[4];  // per wave: its lowest-nonce hit
+    unsigned int found[4];
+};
+__device__ __forceinline__ FirstState& first_state() {
+    __shared__ FirstState fs;
+    return fs;
+}
+
+// MODE 2 slow path: the exact 64-bit test of one candidate (hh, nn wave-uniform) that
+// passed the high-word prune.  The wave keeps its lowest-nonce hit; a new one also lowers
+// the shared bound, which every workgroup reads at its next grab to skip the parts that
+// lie wholly above it.
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v);  // below
+
+// Every word read from LDS goes straight back to scalar registers (uniform64 /
+// readfirstlane) and the tests run in order, so the path holds one or two VGPRs at a time:
+// it sits inside the per-nonce loop, where the plain kernels' 64 VGPRs are all taken.
+__device__ __forceinline__ void first_hit(unsigned long long hh, unsigned long long nn) {
+    FirstState& fs = first_state();
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (hh > uniform64(fs.target)) return;
+    if (__builtin_amdgcn_readfirstlane(fs.found[w]) && nn >= uniform64(fs.n[w])) return;
+    if ((threadIdx.x & 63u) == 0) {
+        fs.n[w] = nn;
+        fs.h[w] = hh;
+        fs.found[w] = 1u;
+        atomicMin(fs.bound, nn);
+    }
+}
+
 // Rounds 0..63 of block B when its whole message schedule is wave-uniform (C2 layouts
 // whose loop digits are the only digits in block B): kw[t] = K[t] + W_t comes from a
 // table, the per-lane input is the state s after block B-1 (= cv), so a nonce costs 64
@@ -284,6 +331,24 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
                 // k = D.base + p·R + r; nonce = k·stride + tail (tail-digit launches, plan.h)
                 unsigned long long n = (D.base + (unsigned long long)p * D.R + r) * D.stride + D.tail;
                 dump[n - dump_lo] = ((unsigned long long)H0 << 32) | H1;
+            }
+        } else if constexpr (MODE == 2) {
+            // first hit: the same wave-uniform prune, against the target's high word
+            // (dump_lo carries the target); the rare slow path tests all 64 bits
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {
+                const bool ok = lane_ok && r >= rlo && r <= rhi;
+                m = __builtin_amdgcn_ballot_w64(H0 <= wb.T && ok);
+                while (m) {
+                    const int l = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                    const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                    const uint32_t pl = __builtin_amdgcn_readlane(p, l);
+                    const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                    const unsigned long long nn = (D.base + (unsigned long long)pl * D.R + r) * D.stride + D.tail;
+                    first_hit(hh, nn);
+                }
             }
         } else {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
@@ -453,6 +518,21 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
 #endif
         if constexpr (MODE == 1) {
             if (lane_ok) dump[D.base + (unsigned long long)r * D.RQ + x - dump_lo] = ((unsigned long long)H0 << 32) | H1;
+        } else if constexpr (MODE == 2) {
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {  // first hit: as scan_row's MODE 2
+                m = __builtin_amdgcn_ballot_w64(H0 <= wb.T && lane_ok);
+                while (m) {
+                    const int l = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                    const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                    const uint32_t xl = __builtin_amdgcn_readlane(x, l);
+                    const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                    const unsigned long long nn = D.base + (unsigned long long)r * D.RQ + xl;
+                    first_hit(hh, nn);
+                }
+            }
         } else {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // wave-uniform, rare once T has settled
@@ -529,6 +609,13 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         clk[1] = __builtin_amdgcn_s_memrealtime();
     }
     WaveBest wb{~0ull, ~0ull, 0xFFFFFFFFu};
+    if constexpr (MODE == 2) {  // dump_lo = the target
+        wb.T = (uint32_t)(dump_lo >> 32);
+        FirstState& fs = first_state();
+        if (tid == 0) { fs.target = dump_lo; fs.bound = thresh; }
+        if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
+        __syncthreads();
+    }
     for (;;) {
         if (tid == 0) {
             const unsigned long long cur = __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -537,10 +624,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             g = g < gmin ? gmin : (g > gmax ? gmax : g);
             sh_grab[0] = atomicAdd(work, g);
             sh_grab[1] = g;
+            if constexpr (MODE == 2)  // the bound of this grab, broadcast with the grab itself
+                first_state().grab_bound = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
         unsigned long long x = uniform64(sh_grab[0]);
         const unsigned long long g = uniform64(sh_grab[1]);
+        unsigned long long grab_bound = ~0ull;
+        if constexpr (MODE == 2) grab_bound = uniform64(first_state().grab_bound);
         __syncthreads();
         if (x >= total) break;
         const unsigned long long end = x + g < total ? x + g : total;
@@ -548,6 +639,26 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             const unsigned long long tv = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)(tv >> 32));
             wb.T = t < wb.T ? t : wb.T;
+        }
+        // MODE 2: `thresh` holds the lowest qualifying nonce found so far by any workgroup
+        // (all ones: none yet).  Thread 0 read it once, at the grab, and every wave took
+        // that one value between the grab's two barriers: the skip decisions below MUST be
+        // the same in all four waves, because scan_row<.., C2 = 2, ..> synchronises the
+        // workgroup (its LDS batches), and a wave that loaded the word itself could see
+        // another workgroup's atomicMin that its neighbours missed.
+        // The bound never drops below the answer, so a part whose every nonce lies above it
+        // cannot hold the answer and is skipped unhashed; every nonce below the answer is
+        // still hashed, in whatever order the workgroups run.  Nothing is added per nonce:
+        // work is left out only here, part by part, and (below) by taking the rest of a
+        // descriptor off the work counter, on the same test.
+        // The bound is held and compared as two 32-bit halves, scalar compares both: a 64-bit
+        // compare is a VALU instruction here and would keep a VGPR copy of the bound alive
+        // through the per-nonce loop (the empty asm keeps the halves from being re-joined).
+        uint32_t bound_hi = ~0u, bound_lo = ~0u;
+        if constexpr (MODE == 2) {
+            bound_hi = (uint32_t)(grab_bound >> 32);
+            bound_lo = (uint32_t)grab_bound;
+            asm volatile("" : "+s"(bound_hi), "+s"(bound_lo));
         }
         while (x < end) {
             int i = 0;
@@ -557,6 +668,30 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             const uint32_t row = rel / D.R, r0 = rel - row * D.R;
             const unsigned long long left = end - x;
             const uint32_t r1 = (unsigned long long)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
+            if constexpr (MODE == 2) {
+                const unsigned long long lb = part_min_nonce(D, C2, row, r0);
+                const uint32_t lh = (uint32_t)(lb >> 32), ll = (uint32_t)lb;
+                if (lh > bound_hi || (lh == bound_hi && ll > bound_lo)) {  // lb > bound
+                    if constexpr (C2 != 3) {
+                        // The second way work is left out.  Within a descriptor a part's
+                        // smallest nonce only grows with its position (row, then r), so every
+                        // later part of this descriptor lies above the bound too: thread 0
+                        // takes them off the work counter in one step, and a launch drains in
+                        // a few grabs per descriptor once a hit is known.  Only
+                        // positions from this part on, in this descriptor, are cancelled.
+                        // At the top of uint64 part_min_nonce can wrap for a LATER part, but
+                        // only where its exact value passes 2^64-1, i.e. where the part holds
+                        // no nonce of the range (plan.h), so cancelling it loses nothing; this
+                        // part's own value, being above the bound, has not wrapped below it.
+                        const unsigned long long dend = offs[i + 1];
+                        if (tid == 0) atomicMax(work, dend);
+                        x = dend < end ? dend : end;
+                    } else {
+                        x += r1 - r0;  // lane table: the next row starts lower again
+                    }
+                    continue;
+                }
+            }
             if constexpr (C2 == 3) scan_row_lt<MODE>(D, row, r0, r1, wb, dump, dump_lo, ktab);
             else scan_row<J, C2, EX, MODE>(D, row, r0, r1, wb, dump, dump_lo, ktab);
             x += r1 - r0;
@@ -585,6 +720,30 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                 const unsigned int idx = atomicAdd(ncand, 1u);
                 cands[idx].hash = bh;
                 cands[idx].nonce = bn;
+            }
+        }
+    }
+    if constexpr (MODE == 2) {
+        // the workgroup's lowest-nonce hit, appended only if it has one (the host reads
+        // "found" off the append counter).  The pair is stored SWAPPED, nonce in .hash, so
+        // k_reduce's lexicographic minimum picks the lowest nonce.
+        const FirstState& fs = first_state();
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long bn = 0, bh = 0;
+            unsigned int any = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (fs.found[i] && (!any || fs.n[i] < bn)) {
+                    bn = fs.n[i];
+                    bh = fs.h[i];
+                    any = 1;
+                }
+            }
+            if (any) {
+                const unsigned int idx = atomicAdd(ncand, 1u);
+                cands[idx].hash = bn;
+                cands[idx].nonce = bh;
             }
         }
     }

@@ -45,6 +45,7 @@ EXPORTED = [
     "gpuhash_open", "gpuhash_ndevices", "gpuhash_device_count", "gpuhash_shard_range",
     "gpuhash_shard_range_policy",
     "gpuhash_set_layout_policy", "gpuhash_min", "gpuhash_min_ex",
+    "gpuhash_first_below", "gpuhash_first_below_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
@@ -144,6 +145,12 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
     lib.gpuhash_min_ex.argtypes = [vp, u8p, sz, u64, u64, ctypes.c_uint32,
                                    ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.gpuhash_min_ex.restype = ctypes.c_int
+    lib.gpuhash_first_below.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                        ctypes.POINTER(ctypes.c_int)]
+    lib.gpuhash_first_below.restype = ctypes.c_int
+    lib.gpuhash_first_below_ex.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64),
+                                           ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int)]
+    lib.gpuhash_first_below_ex.restype = ctypes.c_int
     lib.gpuhash_hash_range.argtypes = [vp, u8p, sz, u64, u64, vp]
     lib.gpuhash_hash_range.restype = ctypes.c_int
     lib.gpuhash_hash_cpu.argtypes = [u8p, sz, u64]
@@ -241,6 +248,24 @@ class Engine:
         if rc != GPUHASH_OK:
             raise GpuHashError(rc, "gpuhash_min")
         return int(h.value), int(n.value)
+
+    def first_below(self, msg, lower: int, upper: int, target: int, rchunk: int = 0) -> tuple[int, int] | None:
+        """(hash, nonce) of the LOWEST nonce n of the inclusive [lower, upper] with
+        Hash(msg, n) <= target -- what an ascending scan that stops at its first hit returns
+        -- or None when no nonce of the range qualifies (gpuhash_first_below_ex).  Arguments
+        are checked as for min()."""
+        _check_u64("lower", lower)
+        _check_u64("upper", upper)
+        _check_u64("target", target)
+        if isinstance(rchunk, bool) or not isinstance(rchunk, int) or not 0 <= rchunk < 1 << 32:
+            raise ValueError(f"rchunk={rchunk!r} outside [0, 2^32)")
+        m = _bytes(msg)
+        h, n, found = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        rc = self._lib.gpuhash_first_below_ex(self._ctx, m, len(m), lower, upper, target, rchunk,
+                                              ctypes.byref(h), ctypes.byref(n), ctypes.byref(found))
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_first_below")
+        return (int(h.value), int(n.value)) if found.value else None
 
     def hash_range(self, msg, lower: int, count: int):
         """numpy uint64 array of Hash(msg, lower + i), computed by the scan kernels."""

@@ -58,9 +58,11 @@ extern "C" {
 
 typedef struct gpuhash_ctx gpuhash_ctx;
 
-/* Per-call measurements of the last gpuhash_min / gpuhash_hash_range on a context. */
+/* Per-call measurements of the last gpuhash_min / gpuhash_first_below /
+ * gpuhash_hash_range on a context. */
 typedef struct gpuhash_stats {
-    uint64_t nonces;          /* nonces searched by the last call                     */
+    uint64_t nonces;          /* nonces searched by the last call (gpuhash_first_below: */
+                              /*    those an ascending scan would have examined)        */
     uint32_t launches;        /* scan-kernel launches (all devices)                   */
     uint32_t ndevices;        /* devices that received a non-empty shard              */
     double wall_ms;           /* host wall time of the call                           */
@@ -175,6 +177,31 @@ int gpuhash_min(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t l
  * default).  Exposed for tuning and for parity tests of the chunked paths. */
 int gpuhash_min_ex(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
                    uint64_t upper, uint32_t rchunk, uint64_t *out_hash, uint64_t *out_nonce);
+
+/* The lowest n in the inclusive [lower, upper] with Hash(msg, n) <= target: what an ascending
+ * scan that stops at its first hit returns (proof-of-work's question; gpuhash_min answers
+ * "the least hash").  *out_found = 1 and (*out_hash, *out_nonce) = that nonce and its hash,
+ * or *out_found = 0 (outputs untouched) when no nonce of the range qualifies.  The
+ * comparison is <=, so target = 2^64-1 returns lower.  A nonce of 2^64-1 is a legal answer:
+ * only *out_found says whether there is one.  The answer is exact -- the LOWEST qualifying
+ * nonce, never merely some qualifying nonce -- under every layout policy and rchunk: the
+ * kernels skip work only above a qualifying nonce they have already found,
+ * so the call returns long before the range is exhausted when a hit lies early in it.
+ * Errors, threading, device-guard behaviour, GPUHASH_MAX_MSG, layout policies, slices and
+ * any span up to [0, 2^64-1] are as for gpuhash_min.  Devices take the same contiguous
+ * shards and the lowest-nonce hit wins; a search over several slices stops after the first
+ * slice that has a hit.  Afterwards gpuhash_last_stats().nonces is what the ascending scan
+ * would have examined -- nonce - lower + 1 when found, the span otherwise -- not what the
+ * devices hashed, and gpuhash_last_launches reports the launches that ran.  Replaces
+ * nothing in the reference (its protocol has no target field). */
+int gpuhash_first_below(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
+                        uint64_t upper, uint64_t target, uint64_t *out_hash, uint64_t *out_nonce,
+                        int *out_found);
+
+/* Same search, caller-chosen work-item granularity (as gpuhash_min_ex). */
+int gpuhash_first_below_ex(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
+                           uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t *out_hash,
+                           uint64_t *out_nonce, int *out_found);
 
 /* out[i] = Hash(msg, lower + i) for i < count, computed on the first device by the
  * SAME kernels as gpuhash_min (per-nonce dump mode).  count <= 2^26; lower + count - 1

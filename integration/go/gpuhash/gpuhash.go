@@ -86,5 +86,24 @@ func (e *Engine) Min(data string, lower, upper uint64) (hash, nonce uint64, err 
 	return uint64(h), uint64(n), rcErr(rc)
 }
 
+// FirstBelow returns the lowest nonce n of the inclusive [lower, upper] with
+// bitcoin.Hash(data, n) <= target, and its hash -- what the ascending loop
+//
+//	for n := lower; n <= upper; n++ { if h := bitcoin.Hash(data, n); h <= target { return h, n } }
+//
+// returns; found is false when no nonce of the range qualifies.  The engine stops
+// hashing once a hit is known, so an early hit returns early.
+func (e *Engine) FirstBelow(data string, lower, upper, target uint64) (hash, nonce uint64, found bool, err error) {
+	var h, n C.uint64_t
+	var f C.int
+	var p *C.uint8_t
+	b := []byte(data) // Go-owned, valid for the duration of the call (cgo rules)
+	if len(b) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&b[0]))
+	}
+	rc := C.gpuhash_first_below(e.ctx, p, C.size_t(len(b)), C.uint64_t(lower), C.uint64_t(upper), C.uint64_t(target), &h, &n, &f)
+	return uint64(h), uint64(n), f != 0, rcErr(rc)
+}
+
 // Close releases the devices.
 func (e *Engine) Close() { C.gpuhash_close(e.ctx) }
