@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -16,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "collect.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -31,6 +33,11 @@ constexpr uint64_t kSlicePerDevice = 1ull << 38;
 // the scan kernel writes (start/end s_memtime and s_memrealtime of workgroup 0).
 constexpr size_t kCounterBytes = 40;
 
+// The device hit list of gpuhash_collect_below holds the kernels' Cand entries.
+static_assert(sizeof(Hit) == sizeof(Cand) && offsetof(Hit, hash) == offsetof(Cand, hash) &&
+                  offsetof(Hit, nonce) == offsetof(Cand, nonce),
+              "collect.h's Hit is the layout of the device hit list");
+
 struct Dev {
     int ord = -1;
     int shard = -1;        // position in gpuhash_open's device list
@@ -43,6 +50,11 @@ struct Dev {
     Cand* h_best = nullptr;  // pinned
     unsigned int* h_nhit = nullptr;  // pinned: first-hit mode's candidate count (0 = no hit)
     uint32_t cap = 0;
+    // collecting mode's hit list: allocated on the entry's first collecting call that asks
+    // for a list (GPUHASH_COLLECT_MAX entries, 16 MB, unless GPUHASH_COLLECT_BUFFER says
+    // otherwise), grow-only
+    Cand* d_hits = nullptr;
+    uint32_t hits_cap = 0;
     // launch descriptors + prefix offsets + per-launch work counters, staged through a
     // pinned host buffer and copied once per call
     uint8_t* d_meta = nullptr;
@@ -61,6 +73,8 @@ struct Dev {
     int rc = GPUHASH_OK;
     uint64_t best_h = ~0ull, best_n = ~0ull;
     bool found = false;  // first-hit mode: (best_h, best_n) is a hit
+    uint64_t hit_count = 0;  // collecting mode: qualifying nonces of the shard, exact
+    std::vector<Hit> hits;   // collecting mode: all of them, unordered, if the list held them all
     bool used = false;
     double kernel_ms = 0;
     uint32_t launches = 0;
@@ -172,6 +186,7 @@ static void dev_free(Dev& d) {
     if (d.d_ncand) hipFree(d.d_ncand);
     if (d.d_best) hipFree(d.d_best);
     if (d.d_cands) hipFree(d.d_cands);
+    if (d.d_hits) hipFree(d.d_hits);
     if (d.h_best) hipHostFree(d.h_best);
     if (d.h_nhit) hipHostFree(d.h_nhit);
     if (d.d_meta) hipFree(d.d_meta);
@@ -217,6 +232,16 @@ static int dev_reserve_clk(Dev& d, size_t groups) {
     return GPUHASH_OK;
 }
 
+static int dev_reserve_hits(Dev& d, uint32_t entries) {
+    if (entries <= d.hits_cap) return GPUHASH_OK;
+    if (d.d_hits) hipFree(d.d_hits);
+    d.d_hits = nullptr;
+    d.hits_cap = 0;
+    if (hipMalloc(&d.d_hits, (size_t)entries * sizeof(Cand)) != hipSuccess) return GPUHASH_ENOMEM;
+    d.hits_cap = entries;
+    return GPUHASH_OK;
+}
+
 static int dev_reserve(Dev& d, uint32_t cap, size_t nev) {
     if (cap > d.cap) {
         if (d.d_cands) hipFree(d.d_cands);
@@ -240,12 +265,19 @@ static int dev_reserve(Dev& d, uint32_t cap, size_t nev) {
 // (gpuhash_first_below): d_thresh is the shared bound, the lowest qualifying nonce found so
 // far, `target` travels in the kernels' dump_lo argument, the workgroups append only real
 // hits (nonce and hash swapped, so the same reduce picks the lowest nonce), and the append
-// counter, copied back before the reduce resets it, is the found flag.
+// counter, copied back before the reduce resets it, is the found flag.  mode 3 collects
+// (gpuhash_collect_below): d_thresh is the 64-bit hit counter, zeroed; the kernels append to
+// d_hits while a slot is below `collect_cap`, which they read from d_ncand (0: count only);
+// there is no reduce.  The counter comes back first, then the `count` entries if they all
+// fitted (count <= collect_cap); a list that overflowed is merely some of the hits, which the
+// collector discards (collect.h), so it is not copied.
 static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                    uint32_t rchunk, int mode, unsigned long long* d_dump, int policy,
-                   uint64_t target = 0) {
+                   uint64_t target = 0, uint32_t collect_cap = 0) {
     d.used = true;
     d.found = false;
+    d.hit_count = 0;
+    d.hits.clear();
     d.kernel_ms = 0;
     d.launches = 0;
     d.recs.clear();
@@ -335,6 +367,7 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
     if (rc) return rc;
     if (tab_words && (rc = dev_reserve_ktab(d, tab_words))) return rc;
     if ((rc = dev_reserve_clk(d, groups.size()))) return rc;
+    if (mode == 3 && collect_cap && (rc = dev_reserve_hits(d, collect_cap))) return rc;
     HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, bytes, hipMemcpyHostToDevice, d.stream));
     for (const Tab& t : tabs)
         HIPCHK(launch_ktab(reinterpret_cast<const LaunchDesc*>(d.d_meta + t.desc_byte), d.d_ktab + t.off,
@@ -347,9 +380,12 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
             HIPCHK(launch_ptab(reinterpret_cast<const LaunchDesc*>(d.d_meta + desc_at[g]),
                                (int)groups[g].idx.size(), reinterpret_cast<uint32_t*>(d.d_meta + ptab_at[g]),
                                d.stream));
-    HIPCHK(hipMemsetAsync(d.d_thresh, 0xFF, sizeof(unsigned long long), d.stream));
+    HIPCHK(hipMemsetAsync(d.d_thresh, mode == 3 ? 0 : 0xFF, sizeof(unsigned long long), d.stream));
     HIPCHK(hipMemsetAsync(d.d_best, 0xFF, sizeof(Cand), d.stream));
-    HIPCHK(hipMemsetAsync(d.d_ncand, 0, sizeof(unsigned int), d.stream));
+    if (mode == 3)  // the list's capacity, which the kernels only read (and every call sets anew)
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.d_ncand), (int)collect_cap, 1, d.stream));
+    else
+        HIPCHK(hipMemsetAsync(d.d_ncand, 0, sizeof(unsigned int), d.stream));
     const unsigned int gmax = rchunk ? rchunk : 400u;
     const unsigned int gmin = std::min(10u, gmax);
     // Groups run back to back on the device's stream (each launch's HIP events then time
@@ -368,10 +404,10 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
         a.gmin = gmin;
         a.gmax = gmax;
         a.thresh = d.d_thresh;
-        a.cands = d.d_cands;
+        a.cands = mode == 3 ? d.d_hits : d.d_cands;
         a.ncand = d.d_ncand;
         a.dump = d_dump;
-        a.dump_lo = mode == 2 ? target : lo;
+        a.dump_lo = mode >= 2 ? target : lo;
         a.ktab = groups[g].C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + ptab_at[g]) : d.d_ktab;
         a.grid = grids[g];
         HIPCHK(hipEventRecord(d.ev[2 * g], a.stream));
@@ -380,8 +416,12 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
     }
     if (mode == 2)
         HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_ncand, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
-    if (mode != 1) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
-    HIPCHK(hipMemcpyAsync(d.h_best, d.d_best, sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
+    if (mode == 0 || mode == 2) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
+    if (mode == 3)  // the hit counter, in the pinned word the other modes' best hash uses
+        HIPCHK(hipMemcpyAsync(&d.h_best->hash, d.d_thresh, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              d.stream));
+    else
+        HIPCHK(hipMemcpyAsync(d.h_best, d.d_best, sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * groups.size(), hipMemcpyDeviceToHost, d.stream));
     if ((rc = host_wait(d))) return rc;
     for (size_t g = 0; g < groups.size(); g++) {
@@ -404,6 +444,16 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
                                                nonces, (double)ms, sclk});
     }
     d.launches = (uint32_t)groups.size();
+    if (mode == 3) {
+        d.hit_count = d.h_best->hash;
+        const size_t n = d.hit_count <= collect_cap ? (size_t)d.hit_count : 0;
+        if (n) {
+            d.hits.resize(n);
+            HIPCHK(hipMemcpyAsync(d.hits.data(), d.d_hits, n * sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(hipStreamSynchronize(d.stream));
+        }
+        return GPUHASH_OK;
+    }
     d.best_h = d.h_best->hash;
     d.best_n = d.h_best->nonce;
     if (mode == 2) {  // stored swapped
@@ -412,6 +462,45 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
         d.best_n = d.h_best->hash;
     }
     return GPUHASH_OK;
+}
+
+// Runs job(i), which returns the entry's return code, for the context entries listed in
+// `which`: on the caller's thread when there is one, else each on a host thread of its own.
+// The code lands in the entry's rc; the function's own result is a failure to start a thread.
+template <class Job>
+static int run_entries(gpuhash_ctx* ctx, const std::vector<int>& which, Job&& job) {
+    if (which.size() == 1) {
+        ctx->devs[(size_t)which[0]].rc = job(which[0]);
+        return GPUHASH_OK;
+    }
+    std::vector<std::thread> th;
+    th.reserve(which.size());
+    // Thread creation can fail (std::system_error): the shards already started are
+    // joined before the error is returned, so no joinable std::thread is destroyed.
+    int spawn_rc = GPUHASH_OK;
+    for (size_t k = 0; k < which.size() && spawn_rc == GPUHASH_OK; k++) {
+        const int i = which[k];
+        try {
+            th.emplace_back([&, i] {
+                Dev& d = ctx->devs[(size_t)i];
+                try {
+                    d.rc = job(i);
+                } catch (const std::bad_alloc&) {
+                    d.used = true;
+                    d.rc = GPUHASH_ENOMEM;
+                } catch (...) {  // nothing may escape a std::thread (std::terminate)
+                    d.used = true;
+                    d.rc = GPUHASH_EHIP;
+                }
+            });
+        } catch (const std::bad_alloc&) {
+            spawn_rc = GPUHASH_ENOMEM;
+        } catch (...) {
+            spawn_rc = GPUHASH_EHIP;
+        }
+    }
+    for (auto& t : th) t.join();
+    return spawn_rc;
 }
 
 extern "C" {
@@ -524,40 +613,14 @@ static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint6
     const int n = (int)ctx->devs.size();
     std::vector<Shard> sh = shard_range(msg_len, lower, upper, n, ctx->policy);
     for (auto& d : ctx->devs) { d.used = false; d.rc = GPUHASH_OK; d.kernel_ms = 0; d.launches = 0; }
-    if (n == 1) {
-        ctx->devs[0].rc = dev_run(ctx->devs[0], msg, msg_len, lower, upper, rchunk, mode, nullptr, ctx->policy,
-                                  target);
-    } else {
-        std::vector<std::thread> th;
-        th.reserve((size_t)n);
-        // Thread creation can fail (std::system_error): the shards already started are
-        // joined before the error is returned, so no joinable std::thread is destroyed.
-        int spawn_rc = GPUHASH_OK;
-        for (int i = 0; i < n && spawn_rc == GPUHASH_OK; i++) {
-            if (sh[(size_t)i].empty) continue;
-            try {
-            th.emplace_back([&, i] {
-                Dev& d = ctx->devs[(size_t)i];
-                try {
-                    d.rc = dev_run(d, msg, msg_len, sh[(size_t)i].lo, sh[(size_t)i].hi, rchunk, mode, nullptr,
-                                   ctx->policy, target);
-                } catch (const std::bad_alloc&) {
-                    d.used = true;
-                    d.rc = GPUHASH_ENOMEM;
-                } catch (...) {  // nothing may escape a std::thread (std::terminate)
-                    d.used = true;
-                    d.rc = GPUHASH_EHIP;
-                }
-            });
-            } catch (const std::bad_alloc&) {
-                spawn_rc = GPUHASH_ENOMEM;
-            } catch (...) {
-                spawn_rc = GPUHASH_EHIP;
-            }
-        }
-        for (auto& t : th) t.join();
-        if (spawn_rc) return spawn_rc;
-    }
+    std::vector<int> which;
+    for (int i = 0; i < n; i++)
+        if (n == 1 || !sh[(size_t)i].empty) which.push_back(i);
+    const int spawn_rc = run_entries(ctx, which, [&](int i) {
+        const uint64_t lo = n == 1 ? lower : sh[(size_t)i].lo, hi = n == 1 ? upper : sh[(size_t)i].hi;
+        return dev_run(ctx->devs[(size_t)i], msg, msg_len, lo, hi, rchunk, mode, nullptr, ctx->policy, target);
+    });
+    if (spawn_rc) return spawn_rc;
     for (auto& d : ctx->devs) {
         if (!d.used) continue;
         if (d.rc) return d.rc;
@@ -661,6 +724,109 @@ int gpuhash_first_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, ui
     return gpuhash_first_below_ex(ctx, msg, msg_len, lower, upper, target, 0, out_hash, out_nonce, out_found);
 }
 
+// gpuhash_collect_below_ex: search()'s slices and run_slice()'s shards, with collect.h's
+// collector between the device runs and the outputs.  A slice's shards run concurrently, one
+// per context entry; a re-run of an overflowed sub-range runs alone, on its shard's entry.
+static int collect(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper,
+                   uint64_t target, uint32_t rchunk, uint64_t* out_nonces, uint64_t* out_hashes, size_t cap,
+                   uint64_t* out_total) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    try {
+        auto t0 = std::chrono::steady_clock::now();
+        const uint64_t n = ctx->devs.size();
+        uint64_t per_dev = kSlicePerDevice;  // as search()
+        if (const char* e = std::getenv("GPUHASH_SLICE_NONCES")) {
+            const unsigned long long v = std::strtoull(e, nullptr, 10);
+            if (v > 0) per_dev = v;
+        }
+        const uint64_t slice = per_dev > ~0ull / n ? ~0ull : per_dev * n;
+        // GPUHASH_COLLECT_BUFFER overrides the device list's entries (tests use it to reach
+        // the overflow path on oracle-sized ranges)
+        uint32_t buffer = GPUHASH_COLLECT_MAX;
+        if (const char* e = std::getenv("GPUHASH_COLLECT_BUFFER")) {
+            const unsigned long long v = std::strtoull(e, nullptr, 10);
+            if (v > 0) buffer = (uint32_t)std::min<unsigned long long>(v, GPUHASH_COLLECT_MAX);
+        }
+        gpuhash_stats st{};
+        ctx->recs.clear();
+        uint32_t ndev_used = 0;
+        auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
+            if (n == 1) {
+                batch.push_back(SubRange{lo, hi, 0});
+                return;
+            }
+            const std::vector<Shard> sh = shard_range(msg_len, lo, hi, (int)n, ctx->policy);
+            for (int i = 0; i < (int)n; i++)
+                if (!sh[(size_t)i].empty) batch.push_back(SubRange{sh[(size_t)i].lo, sh[(size_t)i].hi, i});
+        };
+        auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) -> int {
+            for (auto& d : ctx->devs) { d.used = false; d.rc = GPUHASH_OK; d.kernel_ms = 0; d.launches = 0; }
+            std::vector<int> which;
+            std::vector<const SubRange*> of(ctx->devs.size(), nullptr);
+            for (const SubRange& s : batch) {
+                which.push_back(s.shard);
+                of[(size_t)s.shard] = &s;
+            }
+            const int spawn_rc = run_entries(ctx, which, [&](int i) {
+                return dev_run(ctx->devs[(size_t)i], msg, msg_len, of[(size_t)i]->lo, of[(size_t)i]->hi, rchunk, 3,
+                               nullptr, ctx->policy, target, want_list ? buffer : 0u);
+            });
+            if (spawn_rc) return spawn_rc;
+            double batch_max = 0;
+            uint32_t used = 0;
+            for (size_t k = 0; k < batch.size(); k++) {
+                Dev& d = ctx->devs[(size_t)batch[k].shard];
+                if (d.rc) return d.rc;
+                res[k].count = d.hit_count;
+                res[k].hits = std::move(d.hits);
+                d.hits.clear();
+                ctx->recs.insert(ctx->recs.end(), d.recs.begin(), d.recs.end());
+                st.launches += d.launches;
+                st.kernel_ms += d.kernel_ms;
+                batch_max = std::max(batch_max, d.kernel_ms);
+                used++;
+            }
+            st.max_dev_kernel_ms += batch_max;  // the entries of a batch run concurrently
+            ndev_used = std::max(ndev_used, used);
+            return GPUHASH_OK;
+        };
+        Collector<decltype(run), decltype(split)> c(buffer, cap, run, split);
+        if (int rc = c.collect(lower, upper, slice)) return rc;
+        st.ndevices = ndev_used;
+        const uint64_t span = upper - lower;  // every nonce is hashed: no early exit
+        st.nonces = span == ~0ull ? ~0ull : span + 1;
+        st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ctx->last = st;
+        for (size_t i = 0; i < c.held.size(); i++) {
+            out_nonces[i] = c.held[i].nonce;
+            out_hashes[i] = c.held[i].hash;
+        }
+        *out_total = c.total;
+        return GPUHASH_OK;
+    } catch (const std::bad_alloc&) {
+        return GPUHASH_ENOMEM;
+    } catch (...) {  // no C++ exception crosses the C ABI into a Go or Python host
+        return GPUHASH_EHIP;
+    }
+}
+
+int gpuhash_collect_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
+                             uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t* out_nonces,
+                             uint64_t* out_hashes, size_t cap, uint64_t* out_total) {
+    if (!ctx || !out_total || (msg_len && !msg)) return GPUHASH_EINVAL;
+    if (cap > GPUHASH_COLLECT_MAX || (cap > 0 && (!out_nonces || !out_hashes))) return GPUHASH_EINVAL;
+    if (lower > upper) return GPUHASH_EINVAL;
+    if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
+    return collect(ctx, msg, msg_len, lower, upper, target, rchunk, out_nonces, out_hashes, cap, out_total);
+}
+
+int gpuhash_collect_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
+                          uint64_t upper, uint64_t target, uint64_t* out_nonces, uint64_t* out_hashes,
+                          size_t cap, uint64_t* out_total) {
+    return gpuhash_collect_below_ex(ctx, msg, msg_len, lower, upper, target, 0, out_nonces, out_hashes, cap,
+                                    out_total);
+}
+
 int gpuhash_min(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
                 uint64_t upper, uint64_t* out_hash, uint64_t* out_nonce) {
     return gpuhash_min_ex(ctx, msg, msg_len, lower, upper, 0, out_hash, out_nonce);
@@ -746,9 +912,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.4 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.5 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.4 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.5 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

@@ -10,6 +10,10 @@
  *   gpuhash_cli --range MSG LOWER COUNT -> one hash per line (gpuhash_hash_range)
  *   gpuhash_cli --below MSG LOWER UPPER TARGET -> "Result <hash> <nonce>" of the lowest nonce
  *                                         whose hash is <= TARGET, or "None" (gpuhash_first_below)
+ *   gpuhash_cli --all-below MSG LOWER UPPER TARGET [CAP] -> "Total <n>", then one
+ *                                         "Hit <hash> <nonce>" line for each of the lowest CAP
+ *                                         (default GPUHASH_COLLECT_MAX) nonces whose hash is
+ *                                         <= TARGET, ascending (gpuhash_collect_below)
  *   gpuhash_cli --version
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
  */
@@ -41,16 +45,17 @@ int main(int argc, char **argv) {
     }
     const int range_mode = argc == 5 && strcmp(argv[1], "--range") == 0;
     const int below_mode = argc == 6 && strcmp(argv[1], "--below") == 0;
-    if (!range_mode && !below_mode && argc != 4) {
+    const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
+    if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --version\n", argv[0]);
         return 2;
     }
-    const int opt = range_mode || below_mode;
+    const int opt = range_mode || below_mode || all_mode;
     const char *msg = argv[opt ? 2 : 1];
-    uint64_t a, b, target = 0;
+    uint64_t a, b, target = 0, cap = GPUHASH_COLLECT_MAX;
     if (parse_u64(argv[opt ? 3 : 2], &a) || parse_u64(argv[opt ? 4 : 3], &b) ||
-        (below_mode && parse_u64(argv[5], &target))) {
+        ((below_mode || all_mode) && parse_u64(argv[5], &target)) || (argc == 7 && parse_u64(argv[6], &cap))) {
         fprintf(stderr, "bad number\n");
         return 2;
     }
@@ -80,6 +85,34 @@ int main(int argc, char **argv) {
         } else {
             printf("Result %" PRIu64 " %" PRIu64 "\n", h, n);
         }
+    } else if (all_mode) {
+        /* an oversized CAP is the library's argument error to report, so only the
+         * allocation is clamped */
+        const size_t room = cap > GPUHASH_COLLECT_MAX ? GPUHASH_COLLECT_MAX : (size_t)cap;
+        uint64_t *nonces = (uint64_t *)malloc((room ? room : 1) * sizeof(uint64_t));
+        uint64_t *hashes = (uint64_t *)malloc((room ? room : 1) * sizeof(uint64_t));
+        uint64_t total = 0;
+        if (!nonces || !hashes) { free(nonces); free(hashes); gpuhash_close(ctx); return 3; }
+        rc = gpuhash_collect_below(ctx, (const uint8_t *)msg, len, a, b, target, nonces, hashes,
+                                   cap > GPUHASH_COLLECT_MAX ? (size_t)GPUHASH_COLLECT_MAX + 1 : (size_t)cap, &total);
+        if (rc) {
+            status = fail("gpuhash_collect_below", rc);
+        } else {
+            const uint64_t k = total < cap ? total : cap;
+            for (uint64_t i = 0; i < k && !status; i++) {
+                if (gpuhash_hash_cpu((const uint8_t *)msg, len, nonces[i]) != hashes[i] || hashes[i] > target ||
+                    (i && nonces[i] <= nonces[i - 1])) {
+                    fprintf(stderr, "self-check failed at hit %" PRIu64 " (nonce %" PRIu64 ")\n", i, nonces[i]);
+                    status = 4;
+                }
+            }
+            if (!status) {
+                printf("Total %" PRIu64 "\n", total);
+                for (uint64_t i = 0; i < k; i++) printf("Hit %" PRIu64 " %" PRIu64 "\n", hashes[i], nonces[i]);
+            }
+        }
+        free(nonces);
+        free(hashes);
     } else {
         uint64_t h = 0, n = 0;
         rc = gpuhash_min(ctx, (const uint8_t *)msg, len, a, b, &h, &n);

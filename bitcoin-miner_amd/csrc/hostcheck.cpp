@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "collect.h"
 #include "plan.h"
 
 using namespace gpuhash;
@@ -363,6 +364,75 @@ int hostcheck_first_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint
     *found = any ? 1 : 0;
     *pieces_skipped = skipped;
     if (any) { *hash = best_h; *nonce = best_n; }
+    return 0;
+}
+
+// gpuhash_collect_below as the engine runs it: the same collector (collect.h) over the same
+// slices and shards, with each sub-range run replayed in plain C++ from its plan's
+// descriptors, rows, pieces and masks, as hostcheck_first_below replays MODE 2.  What a GPU
+// decides by timing is the order of the appends to the device list, and so which hits a
+// full list drops: order_seed picks the order in which each variant group's pieces are taken
+// (0 ascending, 1 descending, else a shuffle), and within a piece hits are appended lane by
+// lane, which is not ascending either.  The list holds buffer_entries entries (when a list is
+// asked for) and appends past its end are counted and dropped, as in the kernel.  `policy` is
+// the layout policy of this call.  slice_nonces (0: the engine's 2^38) is the slice per shard
+// and nshards the number of context entries.  Returns 0 and *out_total, the lowest
+// min(cap, total) hits in out_nonces / out_hashes (untouched beyond), and in *out_runs how
+// many sub-range runs the collector asked for, re-runs included.
+int hostcheck_collect_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                            uint32_t rchunk, uint64_t target, int policy, uint64_t order_seed,
+                            uint64_t buffer_entries, uint64_t cap, uint64_t slice_nonces, int nshards,
+                            uint64_t* out_nonces, uint64_t* out_hashes, uint64_t* out_total,
+                            uint64_t* out_runs) {
+    if (lower > upper || !out_total || !out_runs || nshards < 1 || (cap && (!out_nonces || !out_hashes)))
+        return -1;
+    uint64_t runs = 0;
+    Rng rng{order_seed};
+    const uint64_t B = std::max<uint64_t>(buffer_entries, 1);
+    auto run_one = [&](const SubRange& sub, bool want_list, SubResult& out) {
+        runs++;
+        const uint64_t room = want_list ? B : 0;  // the word the kernel reads its capacity from
+        std::vector<Launch> plan;
+        plan_range(msg, len, sub.lo, sub.hi, plan, rchunk, policy, /*host_ptab=*/true);
+        for (const VGroup& g : group_plan(plan, rchunk)) {  // back to back, one counter and list
+            std::vector<size_t> order(g.pieces.size());
+            for (size_t i = 0; i < order.size(); i++) order[i] = i;
+            if (order_seed == 1) std::reverse(order.begin(), order.end());
+            else if (order_seed != 0)
+                for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
+            std::vector<Part> parts;
+            for (size_t k : order) {
+                parts.clear();
+                cut_parts(g, g.pieces[k].first, g.pieces[k].second, parts);
+                for (const Part& pt : parts)
+                    for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                        const uint64_t h = replay_hash(*pt.l, p, r);
+                        if (h > target) return;
+                        const uint64_t slot = out.count++;  // the atomic add
+                        if (slot < room) out.hits.push_back(Hit{h, n});
+                    });
+            }
+        }
+    };
+    auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) {
+        for (size_t i = 0; i < batch.size(); i++) run_one(batch[i], want_list, res[i]);
+        return 0;
+    };
+    auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
+        const std::vector<Shard> sh = shard_range(len, lo, hi, nshards, policy);
+        for (int i = 0; i < nshards; i++)
+            if (!sh[(size_t)i].empty) batch.push_back(SubRange{sh[(size_t)i].lo, sh[(size_t)i].hi, i});
+    };
+    const uint64_t per = slice_nonces ? slice_nonces : 1ull << 38;
+    const uint64_t slice = per > ~0ull / (uint64_t)nshards ? ~0ull : per * (uint64_t)nshards;
+    Collector<decltype(run), decltype(split)> c(B, (size_t)cap, run, split);
+    if (int rc = c.collect(lower, upper, slice)) return rc;
+    for (size_t i = 0; i < c.held.size(); i++) {
+        out_nonces[i] = c.held[i].nonce;
+        out_hashes[i] = c.held[i].hash;
+    }
+    *out_total = c.total;
+    *out_runs = runs;
     return 0;
 }
 

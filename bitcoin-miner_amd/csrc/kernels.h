@@ -22,12 +22,15 @@ struct ScanArgs {
                                      // s_memrealtime of workgroup 0 at its start and its end
     unsigned int gmin, gmax;         // piece size bounds (r values per grab)
     unsigned long long* thresh;      // pruning threshold (monotone atomicMin), per job;
-                                     // MODE 2: the lowest qualifying nonce found so far
+                                     // MODE 2: the lowest qualifying nonce found so far;
+                                     // MODE 3: the 64-bit hit counter (zeroed by the host)
     Cand* cands;                     // appended per-workgroup candidates (MODE 2: only real
-                                     // hits, stored swapped: nonce in .hash, hash in .nonce)
-    unsigned int* ncand;             // append counter
+                                     // hits, stored swapped: nonce in .hash, hash in .nonce);
+                                     // MODE 3: the hit list, {hash, nonce}
+    unsigned int* ncand;             // append counter; MODE 3: the hit list's capacity in
+                                     // entries, which the kernel only reads
     unsigned long long* dump;        // MODE 1 only: per-nonce hashes
-    unsigned long long dump_lo;      // MODE 1: nonce of dump[0]; MODE 2: the target
+    unsigned long long dump_lo;      // MODE 1: nonce of dump[0]; MODE 2 and 3: the target
     const uint32_t* ktab;            // C2/J=0 only: per-r K+W tables (see LaunchDesc::tab_off)
     unsigned int grid;               // workgroups (<= resident capacity, see grid_for)
 };
@@ -36,7 +39,8 @@ struct ScanArgs {
 unsigned int grid_for(int J, int C2, int EX, int mode, int device);
 
 // One persistent launch of the (J, C2, EX) variant over a.descs[0..ndesc).  mode 0: argmin
-// search, 1: per-nonce dump, 2: first hit at or below a target (gpuhash_first_below).
+// search, 1: per-nonce dump, 2: first hit at or below a target (gpuhash_first_below), 3: every
+// hit at or below a target, counted and listed (gpuhash_collect_below).
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a);
 // Fills the uniform K+W table of a C2/J=0 descriptor: tab[64*r + t] = K[t] + W_t(r),
 // r in [0, D.R), for block B's words U with the loop digits of r inserted into W_0.

@@ -7,7 +7,8 @@
 //                      max-ILP scheduling
 //   kernels_misc.hip   C2 = 1/J = 1, C2 = 2, extra-block layouts: max-ILP scheduling
 // The first-hit instances (MODE 2) of each family are in kernels_{plain,ut,misc}_first.hip,
-// built with that family's options.
+// built with that family's options, and the collecting instances (MODE 3) likewise in
+// kernels_{plain,ut,misc}_collect.hip.
 // kernels.hip launches them through these declarations only, so nothing is implicitly
 // instantiated there.
 #pragma once

@@ -28,6 +28,12 @@
 // so far, and parts of the work that lie wholly above it are skipped unhashed (k_scan, at
 // the grab).  Its instances live in kernels_*_first.hip; MODE 0 and MODE 1 compile to the
 // same machine code with or without it.
+//
+// MODE 3 is the third, gpuhash_collect_below: EVERY nonce whose hash is at or below a target,
+// counted exactly and listed while the device list has room (CollectState, below).  The same
+// per-nonce compare and ballot; the slow path appends.  Its instances live in
+// kernels_*_collect.hip, and MODE 0, 1 and 2 compile to the same machine code with or
+// without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -208,6 +214,62 @@ __device__ __forceinline__ void first_hit(unsigned long long hh, unsigned long l
     }
 }
 
+// MODE 3 (collect, gpuhash_collect_below): every nonce whose hash is at or below a target is
+// counted, and appended to a device list while the list has room.  k_scan's arguments are
+// reused, none is added:
+//   thresh   the 64-bit hit counter (the host zeroes it): the number of qualifying nonces
+//   cands    the hit list, Cand{hash, nonce}
+//   *ncand   the list's capacity in entries, READ-ONLY here (0: count only)
+//   dump_lo  the target; wb.T is its high word, as in MODE 2
+// The per-nonce test is MODE 2's compare and ballot.  The slow path has no bound, no skip
+// rule and no per-wave state: one atomic add per ballot reserves popcount(ballot) consecutive
+// slots, and the hits of the ballot are stored at them in lane order while slot < capacity.
+// Hits past the capacity are counted, not stored, so the counter is exact whatever the list
+// holds, and the host re-runs a range whose count exceeds the capacity (collect.h).  The
+// counter is 64-bit: a 2^38-nonce slice under a dense target passes 2^32 hits.
+// As in MODE 2 the state lives in LDS and every word read from it goes straight back to
+// scalar registers, so nothing new is live across the per-nonce loop.  The stores are lane 0's
+// ordinary vector stores of wave-uniform values.
+struct CollectState {
+    unsigned long long* count;
+    Cand* list;
+    uint32_t cap;
+    uint32_t target_lo;
+};
+__device__ __forceinline__ CollectState& collect_state() {
+    __shared__ CollectState cs;
+    return cs;
+}
+
+// The lanes that hold a hit: inside the launch's edges (`ok`) and hash <= target, all 64 bits
+// (T is the target's high word).
+__device__ __forceinline__ unsigned long long collect_ballot(uint32_t H0, uint32_t H1, uint32_t T, bool ok) {
+    const uint32_t tlo = __builtin_amdgcn_readfirstlane(collect_state().target_lo);
+    return __builtin_amdgcn_ballot_w64(ok && (H0 < T || (H0 == T && H1 <= tlo)));
+}
+
+// Counts the hits of ballot m (non-empty) and returns the slot of its first one.
+__device__ __forceinline__ unsigned long long collect_reserve(unsigned long long m) {
+    unsigned long long old = 0;
+    if ((threadIdx.x & 63u) == 0)
+        old = atomicAdd(collect_state().count, (unsigned long long)__builtin_popcountll(m));
+    return uniform64(old);
+}
+
+__device__ __forceinline__ bool collect_room(unsigned long long slot) {
+    return slot < __builtin_amdgcn_readfirstlane(collect_state().cap);
+}
+
+// slot < capacity (collect_room); hh, nn wave-uniform.
+__device__ __forceinline__ void collect_store(unsigned long long slot, unsigned long long hh,
+                                              unsigned long long nn) {
+    if ((threadIdx.x & 63u) == 0) {
+        Cand* const e = collect_state().list + slot;
+        e->hash = hh;
+        e->nonce = nn;
+    }
+}
+
 // Rounds 0..63 of block B when its whole message schedule is wave-uniform (C2 layouts
 // whose loop digits are the only digits in block B): kw[t] = K[t] + W_t comes from a
 // table, the per-lane input is the state s after block B-1 (= cv), so a nonce costs 64
@@ -348,6 +410,27 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
                     const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
                     const unsigned long long nn = (D.base + (unsigned long long)pl * D.R + r) * D.stride + D.tail;
                     first_hit(hh, nn);
+                }
+            }
+        } else if constexpr (MODE == 3) {
+            // collect: MODE 2's prune; the slow path appends every lane that passes the
+            // edge masks and the exact 64-bit test
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {
+                const bool ok = lane_ok && r >= rlo && r <= rhi;
+                m = collect_ballot(H0, H1, wb.T, ok);
+                if (m) {
+                    unsigned long long slot = collect_reserve(m);
+                    while (m && collect_room(slot)) {
+                        const int l = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                        const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                        const uint32_t pl = __builtin_amdgcn_readlane(p, l);
+                        const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                        const unsigned long long nn = (D.base + (unsigned long long)pl * D.R + r) * D.stride + D.tail;
+                        collect_store(slot++, hh, nn);
+                    }
                 }
             }
         } else {
@@ -533,6 +616,24 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
                     first_hit(hh, nn);
                 }
             }
+        } else if constexpr (MODE == 3) {
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {  // collect: as scan_row's MODE 3
+                m = collect_ballot(H0, H1, wb.T, lane_ok);
+                if (m) {
+                    unsigned long long slot = collect_reserve(m);
+                    while (m && collect_room(slot)) {
+                        const int l = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                        const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                        const uint32_t xl = __builtin_amdgcn_readlane(x, l);
+                        const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                        const unsigned long long nn = D.base + (unsigned long long)r * D.RQ + xl;
+                        collect_store(slot++, hh, nn);
+                    }
+                }
+            }
         } else {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // wave-uniform, rare once T has settled
@@ -614,6 +715,17 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         FirstState& fs = first_state();
         if (tid == 0) { fs.target = dump_lo; fs.bound = thresh; }
         if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
+        __syncthreads();
+    }
+    if constexpr (MODE == 3) {  // dump_lo = the target; thresh, cands, ncand: see CollectState
+        wb.T = (uint32_t)(dump_lo >> 32);
+        if (tid == 0) {
+            CollectState& cs = collect_state();
+            cs.count = thresh;
+            cs.list = cands;
+            cs.cap = *ncand;
+            cs.target_lo = (uint32_t)dump_lo;
+        }
         __syncthreads();
     }
     for (;;) {

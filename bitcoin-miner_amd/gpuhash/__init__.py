@@ -35,6 +35,7 @@ GPUHASH_EHIP = -3
 GPUHASH_ETOOLONG = -4
 GPUHASH_ENOMEM = -5
 GPUHASH_MAX_MSG = 1 << 20
+GPUHASH_COLLECT_MAX = 1 << 20
 LAYOUT_AUTO, LAYOUT_UNIFORM, LAYOUT_CLASSIC, LAYOUT_LANETABLE = 0, 1, 2, 3
 # OR-able flags: tail-digit launches always / never (include/gpuhash.h)
 LAYOUT_TAIL_ALWAYS, LAYOUT_TAIL_NEVER = 16, 32
@@ -46,6 +47,7 @@ EXPORTED = [
     "gpuhash_shard_range_policy",
     "gpuhash_set_layout_policy", "gpuhash_min", "gpuhash_min_ex",
     "gpuhash_first_below", "gpuhash_first_below_ex",
+    "gpuhash_collect_below", "gpuhash_collect_below_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
@@ -151,6 +153,12 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
     lib.gpuhash_first_below_ex.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64),
                                            ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int)]
     lib.gpuhash_first_below_ex.restype = ctypes.c_int
+    lib.gpuhash_collect_below.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                          sz, ctypes.POINTER(u64)]
+    lib.gpuhash_collect_below.restype = ctypes.c_int
+    lib.gpuhash_collect_below_ex.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), sz, ctypes.POINTER(u64)]
+    lib.gpuhash_collect_below_ex.restype = ctypes.c_int
     lib.gpuhash_hash_range.argtypes = [vp, u8p, sz, u64, u64, vp]
     lib.gpuhash_hash_range.restype = ctypes.c_int
     lib.gpuhash_hash_cpu.argtypes = [u8p, sz, u64]
@@ -266,6 +274,36 @@ class Engine:
         if rc != GPUHASH_OK:
             raise GpuHashError(rc, "gpuhash_first_below")
         return (int(h.value), int(n.value)) if found.value else None
+
+    def collect_below(self, msg, lower: int, upper: int, target: int, cap: int = GPUHASH_COLLECT_MAX,
+                      rchunk: int = 0) -> tuple[int, list[tuple[int, int]]]:
+        """(total, hits): the exact number of nonces n of the inclusive [lower, upper] with
+        Hash(msg, n) <= target, and the (hash, nonce) of the LOWEST min(cap, total) of them,
+        ascending by nonce (gpuhash_collect_below_ex).  Every nonce is hashed; built for sparse
+        hits.  A target or a cap (0..GPUHASH_COLLECT_MAX) out of range raises ValueError; the
+        other arguments are checked as for min()."""
+        _check_u64("lower", lower)
+        _check_u64("upper", upper)
+        _check_u64("target", target)
+        if isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap <= GPUHASH_COLLECT_MAX:
+            raise ValueError(f"cap={cap!r} outside [0, GPUHASH_COLLECT_MAX]")
+        if isinstance(rchunk, bool) or not isinstance(rchunk, int) or not 0 <= rchunk < 1 << 32:
+            raise ValueError(f"rchunk={rchunk!r} outside [0, 2^32)")
+        m = _bytes(msg)
+        nonces = (ctypes.c_uint64 * cap)() if cap else None
+        hashes = (ctypes.c_uint64 * cap)() if cap else None
+        total = ctypes.c_uint64()
+        rc = self._lib.gpuhash_collect_below_ex(self._ctx, m, len(m), lower, upper, target, rchunk,
+                                                nonces, hashes, cap, ctypes.byref(total))
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_collect_below")
+        k = min(cap, int(total.value))
+        return int(total.value), [(int(hashes[i]), int(nonces[i])) for i in range(k)]
+
+    def count_below(self, msg, lower: int, upper: int, target: int, rchunk: int = 0) -> int:
+        """How many nonces of the inclusive [lower, upper] have Hash(msg, n) <= target:
+        collect_below with cap = 0, which lists nothing."""
+        return self.collect_below(msg, lower, upper, target, cap=0, rchunk=rchunk)[0]
 
     def hash_range(self, msg, lower: int, count: int):
         """numpy uint64 array of Hash(msg, lower + i), computed by the scan kernels."""

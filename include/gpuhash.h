@@ -59,11 +59,13 @@ extern "C" {
 typedef struct gpuhash_ctx gpuhash_ctx;
 
 /* Per-call measurements of the last gpuhash_min / gpuhash_first_below /
- * gpuhash_hash_range on a context. */
+ * gpuhash_collect_below / gpuhash_hash_range on a context. */
 typedef struct gpuhash_stats {
     uint64_t nonces;          /* nonces searched by the last call (gpuhash_first_below: */
-                              /*    those an ascending scan would have examined)        */
-    uint32_t launches;        /* scan-kernel launches (all devices)                   */
+                              /*    those an ascending scan would have examined;        */
+                              /*    gpuhash_collect_below: the span, all of it hashed)  */
+    uint32_t launches;        /* scan-kernel launches (all devices; gpuhash_collect_below: */
+                              /*    re-runs of overflowed sub-ranges included)          */
     uint32_t ndevices;        /* devices that received a non-empty shard              */
     double wall_ms;           /* host wall time of the call                           */
     double kernel_ms;         /* sum over devices of HIP-event time of scan launches  */
@@ -202,6 +204,41 @@ int gpuhash_first_below(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, ui
 int gpuhash_first_below_ex(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
                            uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t *out_hash,
                            uint64_t *out_nonce, int *out_found);
+
+/* Every n in the inclusive [lower, upper] with Hash(msg, n) <= target: how many there are, and
+ * the lowest of them (a pool miner's shares; the hit count of a range at a trial target;
+ * gpuhash_first_below answers "the first one").  *out_total = the EXACT number of qualifying
+ * nonces; it saturates at 2^64-1, which only [0, 2^64-1] with target = 2^64-1 reaches.
+ * out_nonces[i], out_hashes[i] for i < min(cap, total) = the LOWEST min(cap, total) qualifying
+ * nonces, ascending by nonce, and their hashes -- never merely some qualifying nonces, under
+ * every layout policy and rchunk and however many devices ran.  Entries from min(cap, total)
+ * on are untouched.  cap == 0 is a pure count; out_nonces and out_hashes may then be null.
+ * The comparison is <=, so target = 2^64-1 counts the span.  A nonce of 2^64-1 is a legal hit.
+ * GPUHASH_EINVAL, checked before any use of ctx's contents: cap > GPUHASH_COLLECT_MAX, null
+ * out_total, cap > 0 with a null array (and gpuhash_min's: null ctx, lower > upper).
+ * Built for SPARSE hits: per nonce it costs what gpuhash_min costs (one compare against the
+ * target's high word and a ballot), and every hit costs an append to a device list of
+ * GPUHASH_COLLECT_MAX entries (16 MB per context entry, allocated on its first collecting
+ * call; env GPUHASH_COLLECT_BUFFER=<entries> overrides the size).  A dense target is still
+ * exact but slower: every wave iteration then takes the append path (one atomic add per
+ * 64 nonces and a store per listed hit; counting 2^28 nonces at target 2^62, a quarter of
+ * them hits, took 6x gpuhash_min's time), and a sub-range with more hits than
+ * the list holds is split and run again while the output still has room (once cap hits are
+ * held the rest of the range is only counted).
+ * Every nonce of the range is hashed, there is no early exit: gpuhash_last_stats().nonces is
+ * the span, and gpuhash_last_launches reports what ran, re-runs included.  Errors, threading,
+ * device-guard behaviour, GPUHASH_MAX_MSG, layout policies and tail flags, rchunk, contiguous
+ * shards over the context's entries, slices and any span up to [0, 2^64-1] are as for
+ * gpuhash_min.  Replaces nothing in the reference (its protocol has no target field). */
+#define GPUHASH_COLLECT_MAX (1u << 20)
+int gpuhash_collect_below(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
+                          uint64_t upper, uint64_t target, uint64_t *out_nonces, uint64_t *out_hashes,
+                          size_t cap, uint64_t *out_total);
+
+/* Same collection, caller-chosen work-item granularity (as gpuhash_min_ex). */
+int gpuhash_collect_below_ex(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
+                             uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t *out_nonces,
+                             uint64_t *out_hashes, size_t cap, uint64_t *out_total);
 
 /* out[i] = Hash(msg, lower + i) for i < count, computed on the first device by the
  * SAME kernels as gpuhash_min (per-nonce dump mode).  count <= 2^26; lower + count - 1

@@ -105,5 +105,41 @@ func (e *Engine) FirstBelow(data string, lower, upper, target uint64) (hash, non
 	return uint64(h), uint64(n), f != 0, rcErr(rc)
 }
 
+// CollectBelow returns how many nonces n of the inclusive [lower, upper] have
+// bitcoin.Hash(data, n) <= target, and the lowest max of them with their hashes, ascending
+// by nonce -- what the loop
+//
+//	for n := lower; n <= upper; n++ { if h := bitcoin.Hash(data, n); h <= target { total++; ... } }
+//
+// collects.  max is at most GPUHASH_COLLECT_MAX; max == 0 only counts.  Every nonce is
+// hashed: the call is built for sparse hits (a pool miner's shares).
+func (e *Engine) CollectBelow(data string, lower, upper, target uint64, max int) (total uint64, nonces, hashes []uint64, err error) {
+	var t C.uint64_t
+	var p *C.uint8_t
+	var pn, ph *C.uint64_t
+	b := []byte(data) // Go-owned, valid for the duration of the call (cgo rules)
+	if len(b) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&b[0]))
+	}
+	if max < 0 || max > int(C.GPUHASH_COLLECT_MAX) {
+		return 0, nil, nil, rcErr(C.GPUHASH_EINVAL)
+	}
+	if max > 0 {
+		nonces = make([]uint64, max)
+		hashes = make([]uint64, max)
+		pn = (*C.uint64_t)(unsafe.Pointer(&nonces[0]))
+		ph = (*C.uint64_t)(unsafe.Pointer(&hashes[0]))
+	}
+	rc := C.gpuhash_collect_below(e.ctx, p, C.size_t(len(b)), C.uint64_t(lower), C.uint64_t(upper), C.uint64_t(target), pn, ph, C.size_t(max), &t)
+	if err = rcErr(rc); err != nil {
+		return 0, nil, nil, err
+	}
+	k := uint64(max)
+	if uint64(t) < k {
+		k = uint64(t)
+	}
+	return uint64(t), nonces[:k], hashes[:k], nil
+}
+
 // Close releases the devices.
 func (e *Engine) Close() { C.gpuhash_close(e.ctx) }
