@@ -13,25 +13,17 @@
 #include <memory>
 #include <mutex>
 #include <new>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "collect.h"
 #include "kernels.h"
 #include "plan.h"
+#include "stage.h"
 
 using namespace gpuhash;
 
 namespace {
-
-// Nonces per device in one slice of a search (gpuhash_min_ex): 2^38 is ~8 s of work on
-// one MI355X at config-2 rates.
-constexpr uint64_t kSlicePerDevice = 1ull << 38;
-
-// Per kernel-variant group in the launch metadata: the work counter, then the 4 clock words
-// the scan kernel writes (start/end s_memtime and s_memrealtime of workgroup 0).
-constexpr size_t kCounterBytes = 40;
 
 // The device hit list of gpuhash_collect_below holds the kernels' Cand entries.
 static_assert(sizeof(Hit) == sizeof(Cand) && offsetof(Hit, hash) == offsetof(Cand, hash) &&
@@ -49,23 +41,23 @@ struct Dev {
     Cand* d_best = nullptr;
     Cand* h_best = nullptr;  // pinned
     unsigned int* h_nhit = nullptr;  // pinned: first-hit mode's candidate count (0 = no hit)
-    uint32_t cap = 0;
+    size_t cands_cap = 0;
     // collecting mode's hit list: allocated on the entry's first collecting call that asks
     // for a list (GPUHASH_COLLECT_MAX entries, 16 MB, unless GPUHASH_COLLECT_BUFFER says
     // otherwise), grow-only
     Cand* d_hits = nullptr;
-    uint32_t hits_cap = 0;
+    size_t hits_cap = 0;
     // launch descriptors + prefix offsets + per-launch work counters, staged through a
     // pinned host buffer and copied once per call
     uint8_t* d_meta = nullptr;
     uint8_t* h_meta = nullptr;
-    size_t meta_cap = 0;
+    size_t meta_cap = 0, h_meta_cap = 0;
     // uniform K+W tables of C2/J=0 descriptors (one per digit count), grow-only
     uint32_t* d_ktab = nullptr;
     size_t ktab_cap = 0;  // words
     // pinned copy of the per-group work counters + clock samples (kCounterBytes each)
     unsigned long long* h_clk = nullptr;
-    size_t clk_cap = 0;  // groups
+    size_t clk_cap = 0;  // words
     std::vector<hipEvent_t> ev;
     hipEvent_t done = nullptr;  // blocking-sync event: the end of a call's work (host_wait)
     int wait_mode = 0;          // HostWait
@@ -79,6 +71,15 @@ struct Dev {
     double kernel_ms = 0;
     uint32_t launches = 0;
     std::vector<gpuhash_launch_record> recs;
+
+    void reset() {  // before every batch of a call (Call::run)
+        rc = GPUHASH_OK;
+        found = used = false;
+        hit_count = launches = 0;
+        kernel_ms = 0;
+        hits.clear();
+        recs.clear();
+    }
 };
 
 }  // namespace
@@ -113,6 +114,18 @@ struct DeviceGuard {
     do {                                            \
         if ((expr) != hipSuccess) return GPUHASH_EHIP; \
     } while (0)
+
+// Runs f() for an ABI entry point: no C++ exception crosses the C ABI into a Go or Python host.
+template <class F>
+static int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return GPUHASH_ENOMEM;
+    } catch (...) {
+        return GPUHASH_EHIP;
+    }
+}
 
 // How the host waits for a call's work (GPUHASH_HOST_WAIT, read at gpuhash_open):
 //   poll    (default) hipEventQuery on a completion event: back to back for the first
@@ -197,256 +210,164 @@ static void dev_free(Dev& d) {
     d = Dev{};
 }
 
-static int dev_reserve_meta(Dev& d, size_t bytes) {
-    if (bytes <= d.meta_cap) return GPUHASH_OK;
-    if (d.d_meta) hipFree(d.d_meta);
-    if (d.h_meta) hipHostFree(d.h_meta);
-    d.d_meta = nullptr;
-    d.h_meta = nullptr;
-    d.meta_cap = 0;
-    size_t cap = std::max<size_t>(bytes, 64 * 1024);
-    if (hipMalloc(&d.d_meta, cap) != hipSuccess) return GPUHASH_ENOMEM;
-    if (hipHostMalloc(&d.h_meta, cap, hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
-    d.meta_cap = cap;
+// An entry's buffers only grow: room for n elements, on the device or pinned on the host.
+template <class T>
+static int grow(T*& p, size_t& cap, size_t n, bool pinned = false) {
+    if (n <= cap) return GPUHASH_OK;
+    if (p) pinned ? hipHostFree(p) : hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if ((pinned ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T))) != hipSuccess)
+        return GPUHASH_ENOMEM;
+    cap = n;
     return GPUHASH_OK;
 }
 
-static int dev_reserve_ktab(Dev& d, size_t words) {
-    if (words <= d.ktab_cap) return GPUHASH_OK;
-    if (d.d_ktab) hipFree(d.d_ktab);
-    d.d_ktab = nullptr;
-    d.ktab_cap = 0;
-    if (hipMalloc(&d.d_ktab, words * sizeof(uint32_t)) != hipSuccess) return GPUHASH_ENOMEM;
-    d.ktab_cap = words;
-    return GPUHASH_OK;
-}
+// What one device run is asked for.
+struct ScanJob {
+    ScanMode mode = kScanMin;
+    uint64_t target = 0;                   // kScanFirst, kScanCollect: hashes <= target qualify
+    uint32_t collect_cap = 0;              // kScanCollect: hit-list entries asked for (0: count only)
+    unsigned long long* d_dump = nullptr;  // kScanDump: device array for the range's hashes
+};
 
-static int dev_reserve_clk(Dev& d, size_t groups) {
-    if (groups <= d.clk_cap) return GPUHASH_OK;
-    if (d.h_clk) hipHostFree(d.h_clk);
-    d.h_clk = nullptr;
-    d.clk_cap = 0;
-    const size_t n = std::max<size_t>(groups, 8);
-    if (hipHostMalloc(&d.h_clk, kCounterBytes * n, hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
-    d.clk_cap = n;
-    return GPUHASH_OK;
-}
+// How a mode uses the words the kernels share: the one statement of it on the host (kernels.h's
+// ScanArgs and the phases of dev_run refer here).  Unless a flag says otherwise, d_thresh is a
+// bound that only falls, armed to all ones (kScanMin: the pruning threshold); d_ncand is the
+// append counter of d_cands, armed to 0; dump_lo is the range's first nonce (kScanDump: the
+// nonce of dump[0]); and d_best comes back in h_best.
+struct ModeWiring {
+    // d_thresh is the 64-bit hit counter, armed to 0, and comes back in h_best->hash, instead
+    // of d_best.  d_ncand is the list's capacity (collect_cap; 0: count only), which the
+    // kernels only read.  cands is d_hits; after the wait its `count` entries are copied if
+    // they all fitted (count <= collect_cap): a list that overflowed is merely some of the
+    // hits, which the collector discards (collect.h).
+    bool collects;
+    bool takes_target;  // dump_lo is the target
+    // d_thresh is the lowest qualifying nonce found so far.  The workgroups append only real
+    // hits, nonce and hash swapped, so the same reduce picks the lowest nonce, and d_best comes
+    // back swapped.  The append counter, copied to h_nhit before the reduce, is the found flag.
+    bool first_hit;
+    bool reduces;  // k_reduce folds d_cands into d_best
+};
+constexpr ModeWiring kWiring[] = {
+    /* kScanMin     */ {false, false, false, true},
+    /* kScanDump    */ {false, false, false, false},
+    /* kScanFirst   */ {false, true, true, true},
+    /* kScanCollect */ {true, true, false, false},
+};
 
-static int dev_reserve_hits(Dev& d, uint32_t entries) {
-    if (entries <= d.hits_cap) return GPUHASH_OK;
-    if (d.d_hits) hipFree(d.d_hits);
-    d.d_hits = nullptr;
-    d.hits_cap = 0;
-    if (hipMalloc(&d.d_hits, (size_t)entries * sizeof(Cand)) != hipSuccess) return GPUHASH_ENOMEM;
-    d.hits_cap = entries;
-    return GPUHASH_OK;
-}
-
-static int dev_reserve(Dev& d, uint32_t cap, size_t nev) {
-    if (cap > d.cap) {
-        if (d.d_cands) hipFree(d.d_cands);
-        d.d_cands = nullptr;
-        d.cap = 0;
-        if (hipMalloc(&d.d_cands, (size_t)cap * sizeof(Cand)) != hipSuccess) return GPUHASH_ENOMEM;
-        d.cap = cap;
+// dev_run, phase 1: reserves the entry's buffers, writes and uploads the launch metadata in one
+// copy, and has the device build the tables.  grids[g] = workgroups of group g.
+static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector<unsigned int>& grids) {
+    const size_t ng = st.groups.size(), meta = std::max<size_t>(st.bytes, 64 * 1024);
+    int rc;
+    if ((rc = grow(d.d_meta, d.meta_cap, meta)) || (rc = grow(d.h_meta, d.h_meta_cap, meta, true))) return rc;
+    st.fill(d.h_meta);
+    size_t sumgrid = 0;
+    grids.reserve(ng);
+    for (const StageGroup& g : st.groups) {
+        const unsigned int resident = grid_for(g.J, g.C2, g.EX, job.mode, d.ord);
+        if (resident == 0) return GPUHASH_EHIP;
+        grids.push_back(Stage::grid(g, resident));
+        sumgrid += grids.back();
     }
-    while (d.ev.size() < nev) {
+    // every workgroup of every group may append one candidate before the single reduce
+    if ((rc = grow(d.d_cands, d.cands_cap, std::max<size_t>(sumgrid, 1))) ||
+        (rc = grow(d.d_ktab, d.ktab_cap, st.tab_words)) || (rc = grow(d.d_hits, d.hits_cap, job.collect_cap)) ||
+        (rc = grow(d.h_clk, d.clk_cap, kCounterBytes / 8 * std::max<size_t>(ng, 8), true)))
+        return rc;
+    while (d.ev.size() < 2 * ng) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
         d.ev.push_back(e);
     }
-    return GPUHASH_OK;
-}
-
-// Runs one device's shard.  The planned launches are grouped by kernel variant; each
-// group is ONE persistent launch over all its descriptors (guided self-scheduling, see
-// scan_kernel.h), followed by the candidate reduce.  One 16-byte copy back at the end.
-// mode 1 writes per-nonce hashes to d_dump instead.  mode 2 is the first-hit search
-// (gpuhash_first_below): d_thresh is the shared bound, the lowest qualifying nonce found so
-// far, `target` travels in the kernels' dump_lo argument, the workgroups append only real
-// hits (nonce and hash swapped, so the same reduce picks the lowest nonce), and the append
-// counter, copied back before the reduce resets it, is the found flag.  mode 3 collects
-// (gpuhash_collect_below): d_thresh is the 64-bit hit counter, zeroed; the kernels append to
-// d_hits while a slot is below `collect_cap`, which they read from d_ncand (0: count only);
-// there is no reduce.  The counter comes back first, then the `count` entries if they all
-// fitted (count <= collect_cap); a list that overflowed is merely some of the hits, which the
-// collector discards (collect.h), so it is not copied.
-static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
-                   uint32_t rchunk, int mode, unsigned long long* d_dump, int policy,
-                   uint64_t target = 0, uint32_t collect_cap = 0) {
-    d.used = true;
-    d.found = false;
-    d.hit_count = 0;
-    d.hits.clear();
-    d.kernel_ms = 0;
-    d.launches = 0;
-    d.recs.clear();
-    DeviceGuard guard;
-    HIPCHK(hipSetDevice(d.ord));
-    std::vector<Launch> plan;
-    plan_range(msg, len, lo, hi, plan, rchunk, policy);
-
-    struct Group {
-        int J, C2, EX;
-        std::vector<size_t> idx;
-    };
-    std::vector<Group> groups;
-    for (size_t i = 0; i < plan.size(); i++) {
-        const Launch& l = plan[i];
-        auto it = std::find_if(groups.begin(), groups.end(), [&](const Group& g) {
-            return g.J == l.J && g.C2 == l.C2 && g.EX == l.EX;
-        });
-        if (it == groups.end()) {
-            groups.push_back(Group{l.J, l.C2, l.EX, {}});
-            it = groups.end() - 1;
-        }
-        it->idx.push_back(i);
-    }
-
-    // meta layout: [per group: work counter + 4 clock words, 40 B][per group: offs
-    // (n+1) x 8 B, descs, and for C2 = 3 the launches' p-tables]
-    size_t bytes = kCounterBytes * groups.size();
-    std::vector<size_t> offs_at(groups.size()), desc_at(groups.size()), ptab_at(groups.size());
-    for (size_t g = 0; g < groups.size(); g++) {
-        offs_at[g] = bytes;
-        bytes += 8 * (groups[g].idx.size() + 1);
-        bytes = (bytes + 15) & ~(size_t)15;
-        desc_at[g] = bytes;
-        bytes += sizeof(LaunchDesc) * groups[g].idx.size();
-        bytes = (bytes + 15) & ~(size_t)15;
-        ptab_at[g] = bytes;
-        for (size_t k : groups[g].idx) bytes += sizeof(uint32_t) * plan[k].nptab;
-        bytes = (bytes + 15) & ~(size_t)15;
-    }
-    int rc = dev_reserve_meta(d, bytes);
-    if (rc) return rc;
-    std::memset(d.h_meta, 0, kCounterBytes * groups.size());
-    std::vector<unsigned int> grids(groups.size());
-    // C2/J=0 tables: block B's words depend only on the digit count d, so one table per
-    // d serves every descriptor of that digit group; built by k_ktab from the device
-    // copy of the first such descriptor (at desc_at[g] + k * sizeof(LaunchDesc)).
-    struct Tab { int d; uint32_t off, R; size_t desc_byte; };
-    std::vector<Tab> tabs;
-    size_t tab_words = 0;
-    for (size_t g = 0; g < groups.size(); g++) {
-        auto* offs = reinterpret_cast<unsigned long long*>(d.h_meta + offs_at[g]);
-        auto* descs = reinterpret_cast<LaunchDesc*>(d.h_meta + desc_at[g]);
-        uint32_t ptab_words = 0;
-        unsigned long long acc = 0;
-        for (size_t k = 0; k < groups[g].idx.size(); k++) {
-            const Launch& l = plan[groups[g].idx[k]];
-            const LaunchDesc& D = l.desc;
-            offs[k] = acc;
-            acc += (unsigned long long)((D.p_last - D.p_first) / (uint32_t)kBlock + 1u) * D.R;
-            descs[k] = D;
-            if (l.C2 == 3) {  // lane table: room for this launch's p-table (k_ptab fills it)
-                descs[k].tab_off = ptab_words;
-                ptab_words += l.nptab;
-            }
-            if (l.C2 == 1 && l.J == 0) {
-                auto it = std::find_if(tabs.begin(), tabs.end(), [&](const Tab& t) { return t.d == l.d; });
-                if (it == tabs.end()) {
-                    tabs.push_back(Tab{l.d, (uint32_t)tab_words, D.R, desc_at[g] + k * sizeof(LaunchDesc)});
-                    tab_words += 64ull * D.R;
-                    it = tabs.end() - 1;
-                }
-                descs[k].tab_off = it->off;
-            }
-        }
-        offs[groups[g].idx.size()] = acc;
-        unsigned int full = grid_for(groups[g].J, groups[g].C2, groups[g].EX, mode, d.ord);
-        if (full == 0) return GPUHASH_EHIP;
-        // no more workgroups than minimum-size pieces
-        unsigned long long pieces = (acc + 9) / 10;
-        grids[g] = (unsigned int)std::min<unsigned long long>(full, std::max<unsigned long long>(pieces, 1));
-    }
-    // every workgroup of every group may append one candidate before the single reduce
-    uint32_t sumgrid = 0;
-    for (unsigned int gr : grids) sumgrid += gr;
-    rc = dev_reserve(d, std::max<uint32_t>(sumgrid, 1u), 2 * groups.size());
-    if (rc) return rc;
-    if (tab_words && (rc = dev_reserve_ktab(d, tab_words))) return rc;
-    if ((rc = dev_reserve_clk(d, groups.size()))) return rc;
-    if (mode == 3 && collect_cap && (rc = dev_reserve_hits(d, collect_cap))) return rc;
-    HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, bytes, hipMemcpyHostToDevice, d.stream));
-    for (const Tab& t : tabs)
+    HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, st.bytes, hipMemcpyHostToDevice, d.stream));
+    for (const StageTab& t : st.tabs)
         HIPCHK(launch_ktab(reinterpret_cast<const LaunchDesc*>(d.d_meta + t.desc_byte), d.d_ktab + t.off,
                            t.R, d.stream));
     // lane-table groups: their launches' p-tables, one device thread per block B-1 value
     // (on the host these compressions cost ~0.16 us each, ~7% of a search whose loop
     // values cover only 10^5 lane values each)
-    for (size_t g = 0; g < groups.size(); g++)
-        if (groups[g].C2 == 3)
-            HIPCHK(launch_ptab(reinterpret_cast<const LaunchDesc*>(d.d_meta + desc_at[g]),
-                               (int)groups[g].idx.size(), reinterpret_cast<uint32_t*>(d.d_meta + ptab_at[g]),
-                               d.stream));
-    HIPCHK(hipMemsetAsync(d.d_thresh, mode == 3 ? 0 : 0xFF, sizeof(unsigned long long), d.stream));
+    for (const StageGroup& g : st.groups)
+        if (g.C2 == 3)
+            HIPCHK(launch_ptab(reinterpret_cast<const LaunchDesc*>(d.d_meta + g.desc_at), (int)g.idx.size(),
+                               reinterpret_cast<uint32_t*>(d.d_meta + g.ptab_at), d.stream));
+    return GPUHASH_OK;
+}
+
+// dev_run, phase 2: arms the shared words as kWiring says and launches the groups.
+// Groups run back to back on the device's stream (each launch's HIP events then time
+// that kernel alone, which bench.py's roofline relies on).  Running the small groups
+// on a second stream was measured: a persistent grid launched beside another is not
+// fully dispatched until the other drains, so its events span the whole call, for
+// <= 0.3% less wall time.  All groups append to one candidate list (atomic counter,
+// shared pruning threshold); one reduce at the end folds it.
+static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo,
+                          const std::vector<unsigned int>& grids) {
+    const ModeWiring w = kWiring[job.mode];
+    HIPCHK(hipMemsetAsync(d.d_thresh, w.collects ? 0 : 0xFF, sizeof(unsigned long long), d.stream));
     HIPCHK(hipMemsetAsync(d.d_best, 0xFF, sizeof(Cand), d.stream));
-    if (mode == 3)  // the list's capacity, which the kernels only read (and every call sets anew)
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.d_ncand), (int)collect_cap, 1, d.stream));
+    if (w.collects)  // every call sets the capacity anew
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.d_ncand), (int)job.collect_cap, 1, d.stream));
     else
         HIPCHK(hipMemsetAsync(d.d_ncand, 0, sizeof(unsigned int), d.stream));
-    const unsigned int gmax = rchunk ? rchunk : 400u;
-    const unsigned int gmin = std::min(10u, gmax);
-    // Groups run back to back on the device's stream (each launch's HIP events then time
-    // that kernel alone, which bench.py's roofline relies on).  Running the small groups
-    // on a second stream was measured: a persistent grid launched beside another is not
-    // fully dispatched until the other drains, so its events span the whole call, for
-    // <= 0.3% less wall time.  All groups append to one candidate list (atomic counter,
-    // shared pruning threshold); one reduce at the end folds it.
-    for (size_t g = 0; g < groups.size(); g++) {
+    for (size_t g = 0; g < st.groups.size(); g++) {
+        const StageGroup& G = st.groups[g];
         ScanArgs a{};
         a.stream = d.stream;
-        a.descs = reinterpret_cast<const LaunchDesc*>(d.d_meta + desc_at[g]);
-        a.offs = reinterpret_cast<const unsigned long long*>(d.d_meta + offs_at[g]);
-        a.ndesc = (int)groups[g].idx.size();
-        a.work = reinterpret_cast<unsigned long long*>(d.d_meta + kCounterBytes * g);
-        a.gmin = gmin;
-        a.gmax = gmax;
+        a.descs = reinterpret_cast<const LaunchDesc*>(d.d_meta + G.desc_at);
+        a.offs = reinterpret_cast<const unsigned long long*>(d.d_meta + G.offs_at);
+        a.ndesc = (int)G.idx.size();
+        a.work = reinterpret_cast<unsigned long long*>(d.d_meta + G.work_at);
+        a.gmin = st.gmin;
+        a.gmax = st.gmax;
         a.thresh = d.d_thresh;
-        a.cands = mode == 3 ? d.d_hits : d.d_cands;
+        a.cands = w.collects ? d.d_hits : d.d_cands;
         a.ncand = d.d_ncand;
-        a.dump = d_dump;
-        a.dump_lo = mode >= 2 ? target : lo;
-        a.ktab = groups[g].C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + ptab_at[g]) : d.d_ktab;
+        a.dump = job.d_dump;
+        a.dump_lo = w.takes_target ? job.target : lo;
+        a.ktab = G.C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + G.ptab_at) : d.d_ktab;
         a.grid = grids[g];
         HIPCHK(hipEventRecord(d.ev[2 * g], a.stream));
-        HIPCHK(launch_scan(groups[g].J, groups[g].C2, groups[g].EX, mode, a));
+        HIPCHK(launch_scan(G.J, G.C2, G.EX, job.mode, a));
         HIPCHK(hipEventRecord(d.ev[2 * g + 1], a.stream));
     }
-    if (mode == 2)
+    return GPUHASH_OK;
+}
+
+// dev_run, phase 3: the reduce, the copies back, the call's one wait and the launch records.
+static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, uint64_t hi) {
+    const ModeWiring w = kWiring[job.mode];
+    if (w.first_hit)
         HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_ncand, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
-    if (mode == 0 || mode == 2) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
-    if (mode == 3)  // the hit counter, in the pinned word the other modes' best hash uses
-        HIPCHK(hipMemcpyAsync(&d.h_best->hash, d.d_thresh, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              d.stream));
-    else
-        HIPCHK(hipMemcpyAsync(d.h_best, d.d_best, sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * groups.size(), hipMemcpyDeviceToHost, d.stream));
-    if ((rc = host_wait(d))) return rc;
-    for (size_t g = 0; g < groups.size(); g++) {
+    if (w.reduces) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
+    // d_best, or the hit counter alone, which lands in the pinned h_best->hash
+    const void* result = w.collects ? (const void*)d.d_thresh : d.d_best;
+    const size_t result_bytes = w.collects ? sizeof(unsigned long long) : sizeof(Cand);
+    HIPCHK(hipMemcpyAsync(d.h_best, result, result_bytes, hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * st.groups.size(), hipMemcpyDeviceToHost, d.stream));
+    if (int rc = host_wait(d)) return rc;
+    for (size_t g = 0; g < st.groups.size(); g++) {
+        const StageGroup& G = st.groups[g];
         float ms = 0;
         HIPCHK(hipEventElapsedTime(&ms, d.ev[2 * g], d.ev[2 * g + 1]));
         d.kernel_ms += ms;
-        uint64_t nonces = 0, biggest = 0;
-        const Launch* big = nullptr;
-        for (size_t k : groups[g].idx) {
-            const Launch& l = plan[k];
-            uint64_t n = (l.hi - l.lo) / l.stride + 1;
-            nonces += n;
-            if (!big || n > biggest) { big = &l; biggest = n; }
-        }
         const unsigned long long* c = d.h_clk + (kCounterBytes / 8) * g + 1;
         const double ticks = (double)(c[2] - c[0]), rt = (double)(c[3] - c[1]);
         const double sclk = rt > 0 ? ticks / rt * 100.0 : 0.0;  // s_memrealtime runs at 100 MHz
-        d.recs.push_back(gpuhash_launch_record{d.ord, groups[g].J, groups[g].C2, groups[g].EX,
-                                               big->d, big->c, d.shard, d.stream_dev, lo, hi,
-                                               nonces, (double)ms, sclk});
+        d.recs.push_back(gpuhash_launch_record{d.ord, G.J, G.C2, G.EX, G.d, G.c, d.shard, d.stream_dev, lo, hi,
+                                               G.nonces, (double)ms, sclk});
     }
-    d.launches = (uint32_t)groups.size();
-    if (mode == 3) {
+    d.launches = (uint32_t)st.groups.size();
+    return GPUHASH_OK;
+}
+
+// dev_run, phase 4: the entry's results from what came back.
+static int decode(Dev& d, const ScanJob& job) {
+    if (kWiring[job.mode].collects) {
         d.hit_count = d.h_best->hash;
-        const size_t n = d.hit_count <= collect_cap ? (size_t)d.hit_count : 0;
+        const size_t n = d.hit_count <= job.collect_cap ? (size_t)d.hit_count : 0;
         if (n) {
             d.hits.resize(n);
             HIPCHK(hipMemcpyAsync(d.hits.data(), d.d_hits, n * sizeof(Cand), hipMemcpyDeviceToHost, d.stream));
@@ -456,52 +377,86 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
     }
     d.best_h = d.h_best->hash;
     d.best_n = d.h_best->nonce;
-    if (mode == 2) {  // stored swapped
+    if (kWiring[job.mode].first_hit) {
         d.found = *d.h_nhit > 0;
-        d.best_h = d.h_best->nonce;
-        d.best_n = d.h_best->hash;
+        std::swap(d.best_h, d.best_n);
     }
     return GPUHASH_OK;
 }
 
-// Runs job(i), which returns the entry's return code, for the context entries listed in
-// `which`: on the caller's thread when there is one, else each on a host thread of its own.
-// The code lands in the entry's rc; the function's own result is a failure to start a thread.
-template <class Job>
-static int run_entries(gpuhash_ctx* ctx, const std::vector<int>& which, Job&& job) {
-    if (which.size() == 1) {
-        ctx->devs[(size_t)which[0]].rc = job(which[0]);
+// Runs one device's shard [lo, hi] of a job.  The stage groups the planned launches by kernel
+// variant; each group is ONE persistent launch over all its descriptors (scan_kernel.h).
+static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, uint32_t rchunk,
+                   int policy, const ScanJob& job) {
+    d.used = true;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(d.ord));
+    const Stage st(msg, len, lo, hi, rchunk, policy);
+    std::vector<unsigned int> grids;
+    int rc = stage_upload(d, st, job, grids);
+    if (!rc) rc = arm_and_launch(d, st, job, lo, grids);
+    if (!rc) rc = read_back(d, st, job, lo, hi);
+    return rc ? rc : decode(d, job);
+}
+
+// One ABI call: its device runs, batch by batch, and its statistics and launch records, which
+// finish() publishes.  A batch: sub-ranges that run concurrently, each on its own context entry.
+struct Call {
+    gpuhash_ctx* ctx;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    gpuhash_stats st{};
+
+    explicit Call(gpuhash_ctx* c) : ctx(c) { ctx->recs.clear(); }
+
+    // Runs `job` over the batch: on the caller's thread when it is one sub-range, else each on a
+    // host thread of its own.  Takes the entries' records and times; returns the first failure.
+    int run(const uint8_t* msg, size_t msg_len, uint32_t rchunk, const std::vector<SubRange>& batch,
+            const ScanJob& job) {
+        for (auto& d : ctx->devs) d.reset();
+        auto one = [&](const SubRange& s) {  // nothing may escape a std::thread (std::terminate)
+            Dev& d = ctx->devs[(size_t)s.shard];
+            d.rc = guarded([&] { return dev_run(d, msg, msg_len, s.lo, s.hi, rchunk, ctx->policy, job); });
+        };
+        if (batch.size() == 1) {
+            one(batch[0]);
+        } else {
+            std::vector<std::thread> th;
+            th.reserve(batch.size());
+            // Thread creation can fail (std::system_error): the shards already started are
+            // joined before the error is returned, so no joinable std::thread is destroyed.
+            int spawn_rc = GPUHASH_OK;
+            for (size_t k = 0; k < batch.size() && spawn_rc == GPUHASH_OK; k++)
+                spawn_rc = guarded([&] {
+                    th.emplace_back([&, k] { one(batch[k]); });
+                    return GPUHASH_OK;
+                });
+            for (auto& t : th) t.join();
+            if (spawn_rc) return spawn_rc;
+        }
+        double batch_max = 0;
+        uint32_t used = 0;
+        for (auto& d : ctx->devs) {
+            if (!d.used) continue;
+            if (d.rc) return d.rc;
+            ctx->recs.insert(ctx->recs.end(), d.recs.begin(), d.recs.end());
+            st.launches += d.launches;
+            st.kernel_ms += d.kernel_ms;
+            batch_max = std::max(batch_max, d.kernel_ms);
+            used++;
+        }
+        st.max_dev_kernel_ms += batch_max;  // the entries of a batch run concurrently
+        st.ndevices = std::max(st.ndevices, used);
         return GPUHASH_OK;
     }
-    std::vector<std::thread> th;
-    th.reserve(which.size());
-    // Thread creation can fail (std::system_error): the shards already started are
-    // joined before the error is returned, so no joinable std::thread is destroyed.
-    int spawn_rc = GPUHASH_OK;
-    for (size_t k = 0; k < which.size() && spawn_rc == GPUHASH_OK; k++) {
-        const int i = which[k];
-        try {
-            th.emplace_back([&, i] {
-                Dev& d = ctx->devs[(size_t)i];
-                try {
-                    d.rc = job(i);
-                } catch (const std::bad_alloc&) {
-                    d.used = true;
-                    d.rc = GPUHASH_ENOMEM;
-                } catch (...) {  // nothing may escape a std::thread (std::terminate)
-                    d.used = true;
-                    d.rc = GPUHASH_EHIP;
-                }
-            });
-        } catch (const std::bad_alloc&) {
-            spawn_rc = GPUHASH_ENOMEM;
-        } catch (...) {
-            spawn_rc = GPUHASH_EHIP;
-        }
+
+    // The call examined the nonces [first, last].
+    void finish(uint64_t first, uint64_t last) {
+        const uint64_t span = last - first;
+        st.nonces = span == ~0ull ? ~0ull : span + 1;
+        st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ctx->last = st;
     }
-    for (auto& t : th) t.join();
-    return spawn_rc;
-}
+};
 
 extern "C" {
 
@@ -510,13 +465,7 @@ static int open_impl(const int* devices, int ndevices, gpuhash_ctx** out);
 int gpuhash_open(const int* devices, int ndevices, gpuhash_ctx** out) {
     if (!out || ndevices < 0 || (ndevices > 0 && !devices)) return GPUHASH_EINVAL;
     *out = nullptr;
-    try {
-        return open_impl(devices, ndevices, out);
-    } catch (const std::bad_alloc&) {
-        return GPUHASH_ENOMEM;
-    } catch (...) {
-        return GPUHASH_EHIP;
-    }
+    return guarded([&] { return open_impl(devices, ndevices, out); });
 }
 
 static int open_impl(const int* devices, int ndevices, gpuhash_ctx** out) {
@@ -578,7 +527,7 @@ int gpuhash_shard_range_policy(size_t msg_len, uint64_t lower, uint64_t upper, i
                                uint64_t* out_lower, uint64_t* out_upper) {
     if (nshards < 1 || !out_lower || !out_upper || lower > upper || !valid_policy(policy)) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
-    try {
+    return guarded([&] {
         // the same cost model and cut points as gpuhash_min's in-process shards under the
         // same layout policy (the cuts depend on it)
         const std::vector<Shard> sh = shard_range(msg_len, lower, upper, nshards, policy);
@@ -590,11 +539,7 @@ int gpuhash_shard_range_policy(size_t msg_len, uint64_t lower, uint64_t upper, i
             used += s.empty ? 0 : 1;
         }
         return used;
-    } catch (const std::bad_alloc&) {
-        return GPUHASH_ENOMEM;
-    } catch (...) {
-        return GPUHASH_EHIP;
-    }
+    });
 }
 
 int gpuhash_set_layout_policy(gpuhash_ctx* ctx, int policy) {
@@ -604,101 +549,44 @@ int gpuhash_set_layout_policy(gpuhash_ctx* ctx, int policy) {
     return GPUHASH_OK;
 }
 
-// One slice of a search: sharded over the context's devices, each shard on its own
-// host thread + stream, 16-byte host argmin.  Accumulates into st / ctx->recs.
-// mode 2 (first hit): `any` says a hit exists, and the lowest-nonce hit of the shards wins.
-static int run_slice(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
-                     uint64_t upper, uint32_t rchunk, uint64_t& bh, uint64_t& bn, bool& any,
-                     gpuhash_stats& st, int mode = 0, uint64_t target = 0) {
-    const int n = (int)ctx->devs.size();
-    std::vector<Shard> sh = shard_range(msg_len, lower, upper, n, ctx->policy);
-    for (auto& d : ctx->devs) { d.used = false; d.rc = GPUHASH_OK; d.kernel_ms = 0; d.launches = 0; }
-    std::vector<int> which;
-    for (int i = 0; i < n; i++)
-        if (n == 1 || !sh[(size_t)i].empty) which.push_back(i);
-    const int spawn_rc = run_entries(ctx, which, [&](int i) {
-        const uint64_t lo = n == 1 ? lower : sh[(size_t)i].lo, hi = n == 1 ? upper : sh[(size_t)i].hi;
-        return dev_run(ctx->devs[(size_t)i], msg, msg_len, lo, hi, rchunk, mode, nullptr, ctx->policy, target);
-    });
-    if (spawn_rc) return spawn_rc;
-    for (auto& d : ctx->devs) {
-        if (!d.used) continue;
-        if (d.rc) return d.rc;
-        // host argmin over the per-device 16-byte results
-        if (mode == 2) {
-            if (d.found && (!any || d.best_n < bn)) { bh = d.best_h; bn = d.best_n; any = true; }
-        } else {
-            if (!any || d.best_h < bh || (d.best_h == bh && d.best_n < bn)) { bh = d.best_h; bn = d.best_n; }
-            any = true;
-        }
-        ctx->recs.insert(ctx->recs.end(), d.recs.begin(), d.recs.end());
-        st.launches += d.launches;
-        st.kernel_ms += d.kernel_ms;
-    }
-    return GPUHASH_OK;
-}
-
-// The slice loop of gpuhash_min_ex (mode 0) and gpuhash_first_below_ex (mode 2, where
-// out_found is set and the loop stops after the first slice that has a hit).
+// The slice loop of gpuhash_min_ex and gpuhash_first_below_ex (kScanFirst, where out_found is
+// set and the loop stops after the first slice that has a hit).  Searches longer than a slice
+// (stage.h, slice_width) run as consecutive slices, each sharded over the context's devices,
+// with a host argmin over the per-device 16-byte results.
 static int search(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper,
-                  uint32_t rchunk, int mode, uint64_t target, uint64_t* out_hash, uint64_t* out_nonce,
+                  uint32_t rchunk, const ScanJob& job, uint64_t* out_hash, uint64_t* out_nonce,
                   int* out_found) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        const uint64_t n = ctx->devs.size();
-        // Searches longer than kSlicePerDevice nonces per device run as consecutive
-        // slices: every launch descriptor covers <= 10^10-10^12 nonces (plan.h), so one
-        // slice's plan stays a few hundred descriptors, whatever the span (a 2^64 range
-        // would otherwise plan ~10^9 of them).  A slice is ~8 s of GPU work, so the
-        // per-slice sync and 16-byte merge cost nothing measurable.
-        // GPUHASH_SLICE_NONCES overrides the per-device slice (tests use it to exercise
-        // the slice loop, including its end at 2^64-1, on oracle-sized ranges).
-        uint64_t per_dev = kSlicePerDevice;
-        if (const char* e = std::getenv("GPUHASH_SLICE_NONCES")) {
-            const unsigned long long v = std::strtoull(e, nullptr, 10);
-            if (v > 0) per_dev = v;
+    Call call(ctx);
+    const uint64_t slice = slice_width(ctx->devs.size());
+    const bool first = job.mode == kScanFirst;
+    uint64_t bh = ~0ull, bn = ~0ull;
+    bool any = false;  // first hit: a hit exists
+    std::vector<SubRange> batch;
+    for (uint64_t lo = lower;;) {
+        const uint64_t hi = upper - lo < slice ? upper : lo + (slice - 1);
+        batch.clear();
+        split_slice(msg_len, lo, hi, (int)ctx->devs.size(), ctx->policy, batch);
+        if (int rc = call.run(msg, msg_len, rchunk, batch, job)) return rc;
+        for (const Dev& d : ctx->devs) {
+            if (!d.used || (first && !d.found)) continue;
+            // first hit: the lowest nonce wins; else the lowest (hash, nonce)
+            const bool less = first ? d.best_n < bn : d.best_h < bh || (d.best_h == bh && d.best_n < bn);
+            if (!any || less) { bh = d.best_h; bn = d.best_n; }
+            any = true;
         }
-        const uint64_t slice = per_dev > ~0ull / n ? ~0ull : per_dev * n;
-        uint64_t bh = ~0ull, bn = ~0ull;
-        bool any = false;
-        gpuhash_stats st{};
-        ctx->recs.clear();
-        uint32_t ndev_used = 0;
-        for (uint64_t lo = lower;;) {
-            const uint64_t hi = upper - lo < slice ? upper : lo + (slice - 1);
-            int rc = run_slice(ctx, msg, msg_len, lo, hi, rchunk, bh, bn, any, st, mode, target);
-            if (rc) return rc;
-            double slice_max = 0;
-            uint32_t used = 0;
-            for (auto& d : ctx->devs) {
-                if (!d.used) continue;
-                slice_max = std::max(slice_max, d.kernel_ms);
-                used++;
-            }
-            st.max_dev_kernel_ms += slice_max;  // devices run a slice concurrently
-            ndev_used = std::max(ndev_used, used);
-            if (hi == upper || (mode == 2 && any)) break;
-            lo = hi + 1;
-        }
-        st.ndevices = ndev_used;
-        // first hit: what an ascending scan would have examined
-        uint64_t span = (mode == 2 && any ? bn : upper) - lower;
-        st.nonces = span == ~0ull ? ~0ull : span + 1;
-        st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ctx->last = st;
-        if (mode == 2) {
-            *out_found = any ? 1 : 0;
-            if (!any) return GPUHASH_OK;  // outputs untouched
-        }
-        *out_hash = bh;
-        *out_nonce = bn;
-        return GPUHASH_OK;
-    } catch (const std::bad_alloc&) {
-        return GPUHASH_ENOMEM;
-    } catch (...) {  // no C++ exception crosses the C ABI into a Go or Python host
-        return GPUHASH_EHIP;
+        if (hi == upper || (first && any)) break;
+        lo = hi + 1;
     }
+    // first hit: what an ascending scan would have examined
+    call.finish(lower, first && any ? bn : upper);
+    if (first) {
+        *out_found = any ? 1 : 0;
+        if (!any) return GPUHASH_OK;  // outputs untouched
+    }
+    *out_hash = bh;
+    *out_nonce = bn;
+    return GPUHASH_OK;
 }
 
 int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -706,7 +594,7 @@ int gpuhash_min_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
     if (!ctx || !out_hash || !out_nonce || (msg_len && !msg)) return GPUHASH_EINVAL;
     if (lower > upper) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
-    return search(ctx, msg, msg_len, lower, upper, rchunk, 0, 0, out_hash, out_nonce, nullptr);
+    return guarded([&] { return search(ctx, msg, msg_len, lower, upper, rchunk, ScanJob{}, out_hash, out_nonce, nullptr); });
 }
 
 int gpuhash_first_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -715,7 +603,9 @@ int gpuhash_first_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len,
     if (!ctx || !out_hash || !out_nonce || !out_found || (msg_len && !msg)) return GPUHASH_EINVAL;
     if (lower > upper) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
-    return search(ctx, msg, msg_len, lower, upper, rchunk, 2, target, out_hash, out_nonce, out_found);
+    return guarded([&] {
+        return search(ctx, msg, msg_len, lower, upper, rchunk, ScanJob{kScanFirst, target}, out_hash, out_nonce, out_found);
+    });
 }
 
 int gpuhash_first_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -724,90 +614,41 @@ int gpuhash_first_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, ui
     return gpuhash_first_below_ex(ctx, msg, msg_len, lower, upper, target, 0, out_hash, out_nonce, out_found);
 }
 
-// gpuhash_collect_below_ex: search()'s slices and run_slice()'s shards, with collect.h's
-// collector between the device runs and the outputs.  A slice's shards run concurrently, one
-// per context entry; a re-run of an overflowed sub-range runs alone, on its shard's entry.
+// gpuhash_collect_below_ex: search()'s slices and shards, with collect.h's collector between
+// the device runs and the outputs.  A slice's shards run concurrently, one per context entry;
+// a re-run of an overflowed sub-range runs alone, on its shard's entry.
 static int collect(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper,
                    uint64_t target, uint32_t rchunk, uint64_t* out_nonces, uint64_t* out_hashes, size_t cap,
                    uint64_t* out_total) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    try {
-        auto t0 = std::chrono::steady_clock::now();
-        const uint64_t n = ctx->devs.size();
-        uint64_t per_dev = kSlicePerDevice;  // as search()
-        if (const char* e = std::getenv("GPUHASH_SLICE_NONCES")) {
-            const unsigned long long v = std::strtoull(e, nullptr, 10);
-            if (v > 0) per_dev = v;
+    Call call(ctx);
+    // GPUHASH_COLLECT_BUFFER overrides the device list's entries (tests use it to reach
+    // the overflow path on oracle-sized ranges)
+    const uint64_t env = env_u64("GPUHASH_COLLECT_BUFFER");
+    const uint32_t buffer = env ? (uint32_t)std::min<uint64_t>(env, GPUHASH_COLLECT_MAX) : GPUHASH_COLLECT_MAX;
+    auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
+        split_slice(msg_len, lo, hi, (int)ctx->devs.size(), ctx->policy, batch);
+    };
+    auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) -> int {
+        const ScanJob job{kScanCollect, target, want_list ? buffer : 0u};
+        if (int rc = call.run(msg, msg_len, rchunk, batch, job)) return rc;
+        for (size_t k = 0; k < batch.size(); k++) {
+            Dev& d = ctx->devs[(size_t)batch[k].shard];
+            res[k].count = d.hit_count;
+            res[k].hits = std::move(d.hits);
+            d.hits.clear();
         }
-        const uint64_t slice = per_dev > ~0ull / n ? ~0ull : per_dev * n;
-        // GPUHASH_COLLECT_BUFFER overrides the device list's entries (tests use it to reach
-        // the overflow path on oracle-sized ranges)
-        uint32_t buffer = GPUHASH_COLLECT_MAX;
-        if (const char* e = std::getenv("GPUHASH_COLLECT_BUFFER")) {
-            const unsigned long long v = std::strtoull(e, nullptr, 10);
-            if (v > 0) buffer = (uint32_t)std::min<unsigned long long>(v, GPUHASH_COLLECT_MAX);
-        }
-        gpuhash_stats st{};
-        ctx->recs.clear();
-        uint32_t ndev_used = 0;
-        auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
-            if (n == 1) {
-                batch.push_back(SubRange{lo, hi, 0});
-                return;
-            }
-            const std::vector<Shard> sh = shard_range(msg_len, lo, hi, (int)n, ctx->policy);
-            for (int i = 0; i < (int)n; i++)
-                if (!sh[(size_t)i].empty) batch.push_back(SubRange{sh[(size_t)i].lo, sh[(size_t)i].hi, i});
-        };
-        auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) -> int {
-            for (auto& d : ctx->devs) { d.used = false; d.rc = GPUHASH_OK; d.kernel_ms = 0; d.launches = 0; }
-            std::vector<int> which;
-            std::vector<const SubRange*> of(ctx->devs.size(), nullptr);
-            for (const SubRange& s : batch) {
-                which.push_back(s.shard);
-                of[(size_t)s.shard] = &s;
-            }
-            const int spawn_rc = run_entries(ctx, which, [&](int i) {
-                return dev_run(ctx->devs[(size_t)i], msg, msg_len, of[(size_t)i]->lo, of[(size_t)i]->hi, rchunk, 3,
-                               nullptr, ctx->policy, target, want_list ? buffer : 0u);
-            });
-            if (spawn_rc) return spawn_rc;
-            double batch_max = 0;
-            uint32_t used = 0;
-            for (size_t k = 0; k < batch.size(); k++) {
-                Dev& d = ctx->devs[(size_t)batch[k].shard];
-                if (d.rc) return d.rc;
-                res[k].count = d.hit_count;
-                res[k].hits = std::move(d.hits);
-                d.hits.clear();
-                ctx->recs.insert(ctx->recs.end(), d.recs.begin(), d.recs.end());
-                st.launches += d.launches;
-                st.kernel_ms += d.kernel_ms;
-                batch_max = std::max(batch_max, d.kernel_ms);
-                used++;
-            }
-            st.max_dev_kernel_ms += batch_max;  // the entries of a batch run concurrently
-            ndev_used = std::max(ndev_used, used);
-            return GPUHASH_OK;
-        };
-        Collector<decltype(run), decltype(split)> c(buffer, cap, run, split);
-        if (int rc = c.collect(lower, upper, slice)) return rc;
-        st.ndevices = ndev_used;
-        const uint64_t span = upper - lower;  // every nonce is hashed: no early exit
-        st.nonces = span == ~0ull ? ~0ull : span + 1;
-        st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        ctx->last = st;
-        for (size_t i = 0; i < c.held.size(); i++) {
-            out_nonces[i] = c.held[i].nonce;
-            out_hashes[i] = c.held[i].hash;
-        }
-        *out_total = c.total;
         return GPUHASH_OK;
-    } catch (const std::bad_alloc&) {
-        return GPUHASH_ENOMEM;
-    } catch (...) {  // no C++ exception crosses the C ABI into a Go or Python host
-        return GPUHASH_EHIP;
+    };
+    Collector<decltype(run), decltype(split)> c(buffer, cap, run, split);
+    if (int rc = c.collect(lower, upper, slice_width(ctx->devs.size()))) return rc;
+    call.finish(lower, upper);  // every nonce is hashed: no early exit
+    for (size_t i = 0; i < c.held.size(); i++) {
+        out_nonces[i] = c.held[i].nonce;
+        out_hashes[i] = c.held[i].hash;
     }
+    *out_total = c.total;
+    return GPUHASH_OK;
 }
 
 int gpuhash_collect_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -817,7 +658,9 @@ int gpuhash_collect_below_ex(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_le
     if (cap > GPUHASH_COLLECT_MAX || (cap > 0 && (!out_nonces || !out_hashes))) return GPUHASH_EINVAL;
     if (lower > upper) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
-    return collect(ctx, msg, msg_len, lower, upper, target, rchunk, out_nonces, out_hashes, cap, out_total);
+    return guarded([&] {
+        return collect(ctx, msg, msg_len, lower, upper, target, rchunk, out_nonces, out_hashes, cap, out_total);
+    });
 }
 
 int gpuhash_collect_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
@@ -839,34 +682,18 @@ int gpuhash_hash_range(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uin
     if (count > (1ull << 26) || lower + (count - 1) < lower) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    auto t0 = std::chrono::steady_clock::now();
-    Dev& d = ctx->devs[0];
-    for (auto& x : ctx->devs) x.used = false;
+    Call call(ctx);
     DeviceGuard guard;
-    HIPCHK(hipSetDevice(d.ord));
-    unsigned long long* dd = nullptr;
-    if (hipMalloc(&dd, count * sizeof(uint64_t)) != hipSuccess) return GPUHASH_ENOMEM;
-    int rc;
-    try {
-        rc = dev_run(d, msg, msg_len, lower, lower + count - 1, 0, 1, dd, ctx->policy);
-    } catch (const std::bad_alloc&) {
-        rc = GPUHASH_ENOMEM;
-    } catch (...) {
+    HIPCHK(hipSetDevice(ctx->devs[0].ord));
+    ScanJob job{kScanDump};
+    if (hipMalloc(&job.d_dump, count * sizeof(uint64_t)) != hipSuccess) return GPUHASH_ENOMEM;
+    const uint64_t last = lower + (count - 1);
+    int rc = guarded([&] { return call.run(msg, msg_len, 0, {SubRange{lower, last, 0}}, job); });
+    if (!rc && hipMemcpy(out, job.d_dump, count * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
         rc = GPUHASH_EHIP;
-    }
-    if (!rc && hipMemcpy(out, dd, count * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = GPUHASH_EHIP;
-    hipFree(dd);
-    if (rc) return rc;
-    gpuhash_stats st{};
-    st.nonces = count;
-    st.launches = d.launches;
-    st.ndevices = 1;
-    st.kernel_ms = st.max_dev_kernel_ms = d.kernel_ms;
-    ctx->recs = d.recs;
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->last = st;
-    return GPUHASH_OK;
+    hipFree(job.d_dump);
+    if (!rc) call.finish(lower, last);
+    return rc;
 }
 
 uint64_t gpuhash_hash_cpu(const uint8_t* msg, size_t msg_len, uint64_t nonce) {

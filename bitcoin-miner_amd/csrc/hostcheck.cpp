@@ -8,10 +8,12 @@
 // and never used to produce a search result.
 #include <algorithm>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "collect.h"
 #include "plan.h"
+#include "stage.h"
 
 using namespace gpuhash;
 
@@ -29,25 +31,30 @@ struct gpuhash_plan_info {
     uint32_t stride, tail;  // tail-digit launches: nonces = tail (mod stride) in [lo, hi]
 };
 
-int gpuhash_plan_count(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
-                       uint32_t rchunk) {
-    if (lower > upper) return -1;
+static std::vector<Launch> plan_of(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                                   uint32_t rchunk, bool host_ptab = false) {
     std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, rchunk, g_policy);
-    return (int)v.size();
+    plan_range(msg, len, lower, upper, v, rchunk, g_policy, host_ptab);
+    return v;
+}
+
+static gpuhash_plan_info plan_info(const Launch& l) {
+    const LaunchDesc& D = l.desc;
+    return gpuhash_plan_info{l.J, l.C2, l.EX, l.d, l.q, l.s, l.lo, l.hi, D.base, l.nblocks,
+                             D.R, D.rchunk, D.nrchunks, D.p_first, D.p_last, D.r_first, D.r_last,
+                             D.stride, D.tail};
+}
+
+int gpuhash_plan_count(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper, uint32_t rchunk) {
+    return lower > upper ? -1 : (int)plan_of(msg, len, lower, upper, rchunk).size();
 }
 
 int gpuhash_plan_get(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
                      uint32_t rchunk, int idx, gpuhash_plan_info* out) {
     if (lower > upper || !out) return -1;
-    std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, rchunk, g_policy);
+    const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
     if (idx < 0 || idx >= (int)v.size()) return -1;
-    const Launch& l = v[(size_t)idx];
-    const LaunchDesc& D = l.desc;
-    *out = gpuhash_plan_info{l.J, l.C2, l.EX, l.d, l.q, l.s, l.lo, l.hi, D.base, l.nblocks,
-                             D.R, D.rchunk, D.nrchunks, D.p_first, D.p_last, D.r_first, D.r_last,
-                             D.stride, D.tail};
+    *out = plan_info(v[(size_t)idx]);
     return 0;
 }
 
@@ -55,15 +62,8 @@ int gpuhash_plan_get(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t 
 int gpuhash_plan_all(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
                      uint32_t rchunk, gpuhash_plan_info* out, int cap) {
     if (lower > upper) return -1;
-    std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, rchunk, g_policy);
-    for (int i = 0; i < (int)v.size() && i < cap; i++) {
-        const Launch& l = v[(size_t)i];
-        const LaunchDesc& D = l.desc;
-        out[i] = gpuhash_plan_info{l.J, l.C2, l.EX, l.d, l.q, l.s, l.lo, l.hi, D.base, l.nblocks,
-                                   D.R, D.rchunk, D.nrchunks, D.p_first, D.p_last, D.r_first, D.r_last,
-                                   D.stride, D.tail};
-    }
+    const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = plan_info(v[(size_t)i]);
     return (int)v.size();
 }
 
@@ -82,10 +82,7 @@ int gpuhash_shard(uint64_t msg_len, uint64_t lower, uint64_t upper, int n, uint6
 // The cost model's price of the plan of [lower, upper] (plan_cost): what a shard of that
 // range really costs under the layouts plan_range picks for it.
 double gpuhash_plan_cost(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper) {
-    if (lower > upper) return -1;
-    std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, 0, g_policy);
-    return plan_cost(v);
+    return lower > upper ? -1 : plan_cost(plan_of(msg, len, lower, upper, 0));
 }
 
 }  // extern "C"
@@ -164,8 +161,7 @@ extern "C" {
 // Replays the kernel's per-nonce computation from launch `idx`'s descriptor.
 int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
                         uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
-    std::vector<Launch> v;
-    plan_range(msg, len, lower, upper, v, rchunk, g_policy, /*host_ptab=*/true);
+    const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk, /*host_ptab=*/true);
     if (idx < 0 || idx >= (int)v.size()) return -1;
     const Launch& l = v[(size_t)idx];
     const LaunchDesc& D = l.desc;
@@ -201,64 +197,63 @@ namespace {
 // One part of a piece, as the kernel's inner loop cuts it: a row of one descriptor and the
 // loop values [r0, r1).
 struct Part {
-    const Launch* l;
+    const Launch* l;      // for the hash replay
+    const LaunchDesc* D;  // the descriptor as the kernel reads it, in the metadata buffer
     uint32_t row, r0, r1;
     uint64_t pos;   // position of (row, r0) in the group's row-iterations
     uint64_t dend;  // end of the part's descriptor there (offs[i + 1])
 };
 
-// One variant group of a plan: its launches and their prefix offsets in row-iterations
-// (dev_run's `offs`), and the pieces the workgroups grab.
+// One variant group as k_scan finds it in the metadata buffer, and the pieces it hands out.
 struct VGroup {
     std::vector<const Launch*> ls;
-    std::vector<uint64_t> offs;
+    const unsigned long long* offs;  // ls.size() + 1 prefix offsets in row-iterations
+    const LaunchDesc* descs;
     std::vector<std::pair<uint64_t, uint64_t>> pieces;  // [x, end)
 };
 
 // Resident workgroups assumed for the grab sizes (8 per CU on 256 CUs; the real figure
 // comes from the occupancy query and only changes how the same work is cut).
-constexpr uint64_t kReplayGrid = 2048;
+constexpr unsigned int kReplayGrid = 2048;
 
-std::vector<VGroup> group_plan(const std::vector<Launch>& plan, uint32_t rchunk) {
-    std::vector<VGroup> gs;
-    std::vector<const Launch*> firsts;
-    for (const Launch& l : plan) {
-        size_t g = 0;
-        while (g < gs.size() && !(firsts[g]->J == l.J && firsts[g]->C2 == l.C2 && firsts[g]->EX == l.EX)) g++;
-        if (g == gs.size()) { gs.emplace_back(); firsts.push_back(&l); }
-        gs[g].ls.push_back(&l);
-    }
-    const uint64_t gmax = rchunk ? rchunk : 400u, gmin = std::min<uint64_t>(10u, gmax);
-    for (VGroup& g : gs) {
-        uint64_t acc = 0;
-        for (const Launch* l : g.ls) {
-            g.offs.push_back(acc);
-            acc += (uint64_t)((l->desc.p_last - l->desc.p_first) / (uint32_t)kBlock + 1u) * l->desc.R;
+// A device run as the engine stages it (stage.h): the buffer fill() wrote, which dev_run
+// uploads, and the groups read back out of it.
+struct Staged {
+    Stage st;
+    std::vector<uint8_t> meta;
+    std::vector<VGroup> groups;
+
+    Staged(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy)
+        : st(msg, len, lo, hi, rchunk, policy, /*host_ptab=*/true), meta(st.bytes) {
+        st.fill(meta.data());
+        for (const StageGroup& sg : st.groups) {
+            VGroup g;
+            for (size_t k : sg.idx) g.ls.push_back(&st.plan[k]);
+            g.offs = reinterpret_cast<const unsigned long long*>(meta.data() + sg.offs_at);
+            g.descs = reinterpret_cast<const LaunchDesc*>(meta.data() + sg.desc_at);
+            const uint64_t total = g.offs[g.ls.size()], grid = Stage::grid(sg, kReplayGrid);
+            // guided self-scheduling: piece = clamp(remaining / (2 * grid), gmin, gmax)
+            for (uint64_t cur = 0; cur < total;) {
+                const uint64_t p = std::clamp<uint64_t>((total - cur) / (2 * grid), st.gmin, st.gmax);
+                g.pieces.push_back({cur, std::min(cur + p, total)});
+                cur += p;
+            }
+            groups.push_back(std::move(g));
         }
-        g.offs.push_back(acc);
-        const uint64_t grid = std::min<uint64_t>(kReplayGrid, std::max<uint64_t>((acc + 9) / 10, 1));
-        // guided self-scheduling: piece = clamp(remaining / (2 * grid), gmin, gmax)
-        for (uint64_t cur = 0; cur < acc;) {
-            uint64_t p = (acc - cur) / (2 * grid);
-            p = p < gmin ? gmin : (p > gmax ? gmax : p);
-            g.pieces.push_back({cur, std::min(cur + p, acc)});
-            cur += p;
-        }
     }
-    return gs;
-}
+};
 
 void cut_parts(const VGroup& g, uint64_t x, uint64_t end, std::vector<Part>& out) {
     const int ndesc = (int)g.ls.size();
     while (x < end) {
         int i = 0;
-        while (i + 1 < ndesc && g.offs[(size_t)i + 1] <= x) i++;
-        const LaunchDesc& D = g.ls[(size_t)i]->desc;
-        const uint32_t rel = (uint32_t)(x - g.offs[(size_t)i]);
+        while (i + 1 < ndesc && g.offs[i + 1] <= x) i++;
+        const LaunchDesc& D = g.descs[i];
+        const uint32_t rel = (uint32_t)(x - g.offs[i]);
         const uint32_t row = rel / D.R, r0 = rel - row * D.R;
         const uint64_t left = end - x;
         const uint32_t r1 = (uint64_t)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
-        out.push_back(Part{g.ls[(size_t)i], row, r0, r1, x, g.offs[(size_t)i + 1]});
+        out.push_back(Part{g.ls[(size_t)i], &D, row, r0, r1, x, g.offs[i + 1]});
         x += r1 - r0;
     }
 }
@@ -268,7 +263,7 @@ void cut_parts(const VGroup& g, uint64_t x, uint64_t end, std::vector<Part>& out
 // lane value (scan_row's lane_ok, rlo, rhi; scan_row_lt has only lane_ok).
 template <class F>
 void for_each_nonce(const Part& pt, F&& f) {
-    const LaunchDesc& D = pt.l->desc;
+    const LaunchDesc& D = *pt.D;
     for (uint32_t t = 0; t < (uint32_t)kBlock; t++) {
         const uint64_t p64 = (uint64_t)D.p_first + (uint64_t)pt.row * 256u + t;
         if (p64 > D.p_last) break;
@@ -294,9 +289,41 @@ struct Rng {  // splitmix64
     }
 };
 
+// The order a group's pieces are taken in: order_seed 0 ascending, 1 descending, else shuffled.
+std::vector<size_t> piece_order(const VGroup& g, uint64_t order_seed, Rng& rng) {
+    std::vector<size_t> order(g.pieces.size());
+    std::iota(order.begin(), order.end(), (size_t)0);
+    if (order_seed == 1) std::reverse(order.begin(), order.end());
+    else if (order_seed != 0)
+        for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
+    return order;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The stage of a device run over [lower, upper] (stage.h), as dev_run builds it.  Per variant
+// group, in launch order and up to cap groups, 14 words of out: J, C2, EX, descriptors, the d
+// and c of its largest launch (as gpuhash_launch_record has them), row-iterations, nonces, the
+// byte positions in the metadata buffer of its counters, prefix offsets, descriptors and p-table
+// room, and the sizes of the last two.  *bytes is the buffer's size, and meta[0, *bytes) the
+// buffer as fill() writes it, if meta_cap allows.  Returns the group count.
+int hostcheck_stage(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper, uint32_t rchunk,
+                    uint64_t* out, int cap, uint64_t* bytes, uint8_t* meta, uint64_t meta_cap) {
+    if (lower > upper || !bytes) return -1;
+    const Stage st(msg, len, lower, upper, rchunk, g_policy);
+    for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
+        const StageGroup& g = st.groups[(size_t)i];
+        const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,
+                                  (uint64_t)g.c, g.total, g.nonces, g.work_at, g.offs_at, g.desc_at, g.ptab_at,
+                                  sizeof(LaunchDesc) * g.idx.size(), g.ptab_bytes};
+        std::memcpy(out + 14 * i, row, sizeof row);
+    }
+    *bytes = st.bytes;
+    if (meta && meta_cap >= st.bytes) st.fill(meta);
+    return (int)st.groups.size();
+}
 
 // The first-hit search of [lower, upper] as the kernels run it.  order_seed picks the order
 // in which each variant group's pieces are taken: 0 ascending, 1 strictly descending, any
@@ -313,25 +340,19 @@ int hostcheck_first_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint
                           uint32_t rchunk, uint64_t target, uint64_t order_seed, uint64_t* hash,
                           uint64_t* nonce, int* found, uint64_t* pieces_skipped) {
     if (lower > upper || !hash || !nonce || !found || !pieces_skipped) return -1;
-    std::vector<Launch> plan;
-    plan_range(msg, len, lower, upper, plan, rchunk, g_policy, /*host_ptab=*/true);
-    const std::vector<VGroup> groups = group_plan(plan, rchunk);
+    const Staged run(msg, len, lower, upper, rchunk, g_policy);
     uint64_t bound = ~0ull;  // the word `thresh` points to
     bool any = false;
     uint64_t best_n = 0, best_h = 0, skipped = 0;
     Rng rng{order_seed};
-    for (const VGroup& g : groups) {  // the groups run back to back on one stream
+    for (const VGroup& g : run.groups) {  // the groups run back to back on one stream
         std::vector<std::pair<uint64_t, uint64_t>> cancelled;  // [from, to) positions
         auto is_cancelled = [&](uint64_t pos) {
             for (const auto& c : cancelled)
                 if (pos >= c.first && pos < c.second) return true;
             return false;
         };
-        std::vector<size_t> order(g.pieces.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        if (order_seed == 1) std::reverse(order.begin(), order.end());
-        else if (order_seed != 0)
-            for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
+        const std::vector<size_t> order = piece_order(g, order_seed, rng);
         for (size_t at = 0; at < order.size();) {
             const size_t batch = order_seed <= 1 ? 1 : std::min<size_t>(1 + rng.next() % 8, order.size() - at);
             const uint64_t seen = bound;  // read once per grab, before the batch publishes
@@ -343,7 +364,7 @@ int hostcheck_first_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint
                 bool all_skipped = true;
                 for (const Part& pt : parts) {
                     if (is_cancelled(pt.pos)) continue;
-                    if (part_min_nonce(pt.l->desc, pt.l->C2, pt.row, pt.r0) > seen) {
+                    if (part_min_nonce(*pt.D, pt.l->C2, pt.row, pt.r0) > seen) {
                         if (pt.l->C2 != 3) cancelled.push_back({pt.pos, pt.dend});
                         continue;
                     }
@@ -375,7 +396,7 @@ int hostcheck_first_below(const uint8_t* msg, uint64_t len, uint64_t lower, uint
 // (0 ascending, 1 descending, else a shuffle), and within a piece hits are appended lane by
 // lane, which is not ascending either.  The list holds buffer_entries entries (when a list is
 // asked for) and appends past its end are counted and dropped, as in the kernel.  `policy` is
-// the layout policy of this call.  slice_nonces (0: the engine's 2^38) is the slice per shard
+// the layout policy of this call.  slice_nonces (0: the engine's, stage.h) is the slice per shard
 // and nshards the number of context entries.  Returns 0 and *out_total, the lowest
 // min(cap, total) hits in out_nonces / out_hashes (untouched beyond), and in *out_runs how
 // many sub-range runs the collector asked for, re-runs included.
@@ -392,16 +413,10 @@ int hostcheck_collect_below(const uint8_t* msg, uint64_t len, uint64_t lower, ui
     auto run_one = [&](const SubRange& sub, bool want_list, SubResult& out) {
         runs++;
         const uint64_t room = want_list ? B : 0;  // the word the kernel reads its capacity from
-        std::vector<Launch> plan;
-        plan_range(msg, len, sub.lo, sub.hi, plan, rchunk, policy, /*host_ptab=*/true);
-        for (const VGroup& g : group_plan(plan, rchunk)) {  // back to back, one counter and list
-            std::vector<size_t> order(g.pieces.size());
-            for (size_t i = 0; i < order.size(); i++) order[i] = i;
-            if (order_seed == 1) std::reverse(order.begin(), order.end());
-            else if (order_seed != 0)
-                for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
+        const Staged staged(msg, len, sub.lo, sub.hi, rchunk, policy);
+        for (const VGroup& g : staged.groups) {  // back to back, one counter and list
             std::vector<Part> parts;
-            for (size_t k : order) {
+            for (size_t k : piece_order(g, order_seed, rng)) {
                 parts.clear();
                 cut_parts(g, g.pieces[k].first, g.pieces[k].second, parts);
                 for (const Part& pt : parts)
@@ -419,14 +434,10 @@ int hostcheck_collect_below(const uint8_t* msg, uint64_t len, uint64_t lower, ui
         return 0;
     };
     auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
-        const std::vector<Shard> sh = shard_range(len, lo, hi, nshards, policy);
-        for (int i = 0; i < nshards; i++)
-            if (!sh[(size_t)i].empty) batch.push_back(SubRange{sh[(size_t)i].lo, sh[(size_t)i].hi, i});
+        split_slice(len, lo, hi, nshards, policy, batch);
     };
-    const uint64_t per = slice_nonces ? slice_nonces : 1ull << 38;
-    const uint64_t slice = per > ~0ull / (uint64_t)nshards ? ~0ull : per * (uint64_t)nshards;
     Collector<decltype(run), decltype(split)> c(B, (size_t)cap, run, split);
-    if (int rc = c.collect(lower, upper, slice)) return rc;
+    if (int rc = c.collect(lower, upper, slice_width((uint64_t)nshards, slice_nonces))) return rc;
     for (size_t i = 0; i < c.held.size(); i++) {
         out_nonces[i] = c.held[i].nonce;
         out_hashes[i] = c.held[i].hash;
@@ -443,10 +454,9 @@ int hostcheck_collect_below(const uint8_t* msg, uint64_t len, uint64_t lower, ui
 int hostcheck_parts(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper, uint32_t rchunk,
                     uint64_t* bound, uint64_t* least, uint64_t* count, int cap) {
     if (lower > upper) return -1;
-    std::vector<Launch> plan;
-    plan_range(msg, len, lower, upper, plan, rchunk, g_policy);
+    const Staged run(msg, len, lower, upper, rchunk, g_policy);
     int n = 0;
-    for (const VGroup& g : group_plan(plan, rchunk)) {
+    for (const VGroup& g : run.groups) {
         for (const auto& pc : g.pieces) {
             std::vector<Part> parts;
             cut_parts(g, pc.first, pc.second, parts);
@@ -457,7 +467,7 @@ int hostcheck_parts(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t u
                         if (!c || x < lo) lo = x;
                         c++;
                     });
-                    bound[n] = part_min_nonce(pt.l->desc, pt.l->C2, pt.row, pt.r0);
+                    bound[n] = part_min_nonce(*pt.D, pt.l->C2, pt.row, pt.r0);
                     least[n] = lo;
                     count[n] = c;
                 }

@@ -12,6 +12,9 @@ struct Cand {
     unsigned long long nonce;
 };
 
+// The arguments of one scan launch.  thresh, cands, ncand and dump_lo mean different things per
+// mode; how the host sets them is stated once, at kWiring in gpuhash.cpp, and how the kernels
+// read them in scan_kernel.h.
 struct ScanArgs {
     hipStream_t stream;
     const LaunchDesc* descs;         // device: the group's launch descriptors
@@ -20,20 +23,18 @@ struct ScanArgs {
     unsigned long long* work;        // device: guided-scheduling counter (zeroed per launch),
                                      // followed by 4 clock words the kernel fills: s_memtime /
                                      // s_memrealtime of workgroup 0 at its start and its end
-    unsigned int gmin, gmax;         // piece size bounds (r values per grab)
-    unsigned long long* thresh;      // pruning threshold (monotone atomicMin), per job;
-                                     // MODE 2: the lowest qualifying nonce found so far;
-                                     // MODE 3: the 64-bit hit counter (zeroed by the host)
-    Cand* cands;                     // appended per-workgroup candidates (MODE 2: only real
-                                     // hits, stored swapped: nonce in .hash, hash in .nonce);
-                                     // MODE 3: the hit list, {hash, nonce}
-    unsigned int* ncand;             // append counter; MODE 3: the hit list's capacity in
-                                     // entries, which the kernel only reads
+    unsigned int gmin, gmax;         // piece size bounds (r values per grab; stage.h)
+    unsigned long long* thresh;      // the shared 64-bit word: a bound or the hit counter
+    Cand* cands;                     // appended candidates, or the hit list
+    unsigned int* ncand;             // append counter, or the hit list's capacity
     unsigned long long* dump;        // MODE 1 only: per-nonce hashes
-    unsigned long long dump_lo;      // MODE 1: nonce of dump[0]; MODE 2 and 3: the target
+    unsigned long long dump_lo;      // nonce of dump[0], or the target
     const uint32_t* ktab;            // C2/J=0 only: per-r K+W tables (see LaunchDesc::tab_off)
     unsigned int grid;               // workgroups (<= resident capacity, see grid_for)
 };
+
+// The scan kernels' MODE template parameter (scan_kernel.h), by name on the host.
+enum ScanMode : int { kScanMin = 0, kScanDump = 1, kScanFirst = 2, kScanCollect = 3 };
 
 // Resident workgroups of 256 threads for the (J, C2, EX, mode) kernel on this device.
 unsigned int grid_for(int J, int C2, int EX, int mode, int device);
