@@ -67,6 +67,10 @@ struct Dev {
     bool found = false;  // first-hit mode: (best_h, best_n) is a hit
     uint64_t hit_count = 0;  // collecting mode: qualifying nonces of the shard, exact
     std::vector<Hit> hits;   // collecting mode: all of them, unordered, if the list held them all
+    // batch mode: the run's result list as it came back, and its fold, one (hash, nonce) per job
+    // of the run
+    std::vector<BatchEntry> bat_list;
+    std::vector<uint64_t> bat_h, bat_n;
     bool used = false;
     double kernel_ms = 0;
     uint32_t launches = 0;
@@ -249,12 +253,19 @@ struct ModeWiring {
     // back swapped.  The append counter, copied to h_nhit before the reduce, is the found flag.
     bool first_hit;
     bool reduces;  // k_reduce folds d_cands into d_best
+    // The mode's words live in the metadata buffer, where the stage's fill() arms them (stage.h):
+    // thresh is the array of per-job pruning words, cands the result list (BatchEntry) and ncand
+    // the list's head, whose append counter comes back in h_nhit.  After the wait that many
+    // entries are copied and folded per job by the (hash, nonce) key.  d_thresh, d_cands, d_ncand
+    // and d_best are not used.
+    bool batch;
 };
 constexpr ModeWiring kWiring[] = {
     /* kScanMin     */ {false, false, false, true},
     /* kScanDump    */ {false, false, false, false},
     /* kScanFirst   */ {false, true, true, true},
     /* kScanCollect */ {true, true, false, false},
+    /* kScanBatch   */ {false, false, false, false, true},
 };
 
 // dev_run, phase 1: reserves the entry's buffers, writes and uploads the launch metadata in one
@@ -262,14 +273,16 @@ constexpr ModeWiring kWiring[] = {
 static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector<unsigned int>& grids) {
     const size_t ng = st.groups.size(), meta = std::max<size_t>(st.bytes, 64 * 1024);
     int rc;
-    if ((rc = grow(d.d_meta, d.meta_cap, meta)) || (rc = grow(d.h_meta, d.h_meta_cap, meta, true))) return rc;
+    const size_t host_meta = std::max<size_t>(st.upload_bytes, 64 * 1024);  // a batch's list is the device's alone
+    if ((rc = grow(d.d_meta, d.meta_cap, meta)) || (rc = grow(d.h_meta, d.h_meta_cap, host_meta, true))) return rc;
     st.fill(d.h_meta);
     size_t sumgrid = 0;
     grids.reserve(ng);
     for (const StageGroup& g : st.groups) {
         const unsigned int resident = grid_for(g.J, g.C2, g.EX, job.mode, d.ord);
         if (resident == 0) return GPUHASH_EHIP;
-        grids.push_back(Stage::grid(g, resident));
+        // a batch stage's list bound assumes at most kBatchMaxGrid workgroups (stage.h)
+        grids.push_back(Stage::grid(g, st.njobs ? std::min<unsigned int>(resident, kBatchMaxGrid) : resident));
         sumgrid += grids.back();
     }
     // every workgroup of every group may append one candidate before the single reduce
@@ -282,7 +295,7 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
         HIPCHK(hipEventCreate(&e));
         d.ev.push_back(e);
     }
-    HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, st.bytes, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, st.upload_bytes, hipMemcpyHostToDevice, d.stream));
     for (const StageTab& t : st.tabs)
         HIPCHK(launch_ktab(reinterpret_cast<const LaunchDesc*>(d.d_meta + t.desc_byte), d.d_ktab + t.off,
                            t.R, d.stream));
@@ -306,12 +319,14 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
 static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo,
                           const std::vector<unsigned int>& grids) {
     const ModeWiring w = kWiring[job.mode];
-    HIPCHK(hipMemsetAsync(d.d_thresh, w.collects ? 0 : 0xFF, sizeof(unsigned long long), d.stream));
-    HIPCHK(hipMemsetAsync(d.d_best, 0xFF, sizeof(Cand), d.stream));
-    if (w.collects)  // every call sets the capacity anew
-        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.d_ncand), (int)job.collect_cap, 1, d.stream));
-    else
-        HIPCHK(hipMemsetAsync(d.d_ncand, 0, sizeof(unsigned int), d.stream));
+    if (!w.batch) {
+        HIPCHK(hipMemsetAsync(d.d_thresh, w.collects ? 0 : 0xFF, sizeof(unsigned long long), d.stream));
+        HIPCHK(hipMemsetAsync(d.d_best, 0xFF, sizeof(Cand), d.stream));
+        if (w.collects)  // every call sets the capacity anew
+            HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d.d_ncand), (int)job.collect_cap, 1, d.stream));
+        else
+            HIPCHK(hipMemsetAsync(d.d_ncand, 0, sizeof(unsigned int), d.stream));
+    }
     for (size_t g = 0; g < st.groups.size(); g++) {
         const StageGroup& G = st.groups[g];
         ScanArgs a{};
@@ -325,6 +340,11 @@ static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t 
         a.thresh = d.d_thresh;
         a.cands = w.collects ? d.d_hits : d.d_cands;
         a.ncand = d.d_ncand;
+        if (w.batch) {
+            a.thresh = reinterpret_cast<unsigned long long*>(d.d_meta + st.thresh_at);
+            a.cands = reinterpret_cast<Cand*>(d.d_meta + st.list_at + kBatchListHead);
+            a.ncand = reinterpret_cast<unsigned int*>(d.d_meta + st.list_at);
+        }
         a.dump = job.d_dump;
         a.dump_lo = w.takes_target ? job.target : lo;
         a.ktab = G.C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + G.ptab_at) : d.d_ktab;
@@ -341,11 +361,13 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
     const ModeWiring w = kWiring[job.mode];
     if (w.first_hit)
         HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_ncand, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
+    if (w.batch)
+        HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_meta + st.list_at, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
     if (w.reduces) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
     // d_best, or the hit counter alone, which lands in the pinned h_best->hash
     const void* result = w.collects ? (const void*)d.d_thresh : d.d_best;
     const size_t result_bytes = w.collects ? sizeof(unsigned long long) : sizeof(Cand);
-    HIPCHK(hipMemcpyAsync(d.h_best, result, result_bytes, hipMemcpyDeviceToHost, d.stream));
+    if (!w.batch) HIPCHK(hipMemcpyAsync(d.h_best, result, result_bytes, hipMemcpyDeviceToHost, d.stream));
     HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * st.groups.size(), hipMemcpyDeviceToHost, d.stream));
     if (int rc = host_wait(d)) return rc;
     for (size_t g = 0; g < st.groups.size(); g++) {
@@ -364,7 +386,25 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
 }
 
 // dev_run, phase 4: the entry's results from what came back.
-static int decode(Dev& d, const ScanJob& job) {
+static int decode(Dev& d, const ScanJob& job, const Stage& st) {
+    if (kWiring[job.mode].batch) {
+        const size_t n = *d.h_nhit;
+        if (n > st.list_cap) return GPUHASH_EHIP;  // the bound is proved (stage.h): not reached
+        d.bat_list.resize(n);
+        if (n) {
+            HIPCHK(hipMemcpyAsync(d.bat_list.data(), d.d_meta + st.list_at + kBatchListHead, n * sizeof(BatchEntry),
+                                  hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(hipStreamSynchronize(d.stream));
+        }
+        d.bat_h.assign(st.njobs, ~0ull);
+        d.bat_n.assign(st.njobs, ~0ull);
+        for (const BatchEntry& e : d.bat_list) {
+            if (e.job >= st.njobs) return GPUHASH_EHIP;
+            uint64_t &h = d.bat_h[e.job], &x = d.bat_n[e.job];
+            if (e.hash < h || (e.hash == h && e.nonce < x)) { h = e.hash; x = e.nonce; }
+        }
+        return GPUHASH_OK;
+    }
     if (kWiring[job.mode].collects) {
         d.hit_count = d.h_best->hash;
         const size_t n = d.hit_count <= job.collect_cap ? (size_t)d.hit_count : 0;
@@ -396,7 +436,25 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
     int rc = stage_upload(d, st, job, grids);
     if (!rc) rc = arm_and_launch(d, st, job, lo, grids);
     if (!rc) rc = read_back(d, st, job, lo, hi);
-    return rc ? rc : decode(d, job);
+    return rc ? rc : decode(d, job, st);
+}
+
+// Runs one entry's run of a sub-batch: the jobs [first, end) of `jobs`, whose plans are moved
+// into the stage; index0 is the batch index of jobs[0], for the launch records.
+static int dev_run_batch(Dev& d, std::vector<PlannedJob>& jobs, size_t first, size_t end, size_t index0,
+                         uint32_t rchunk) {
+    d.used = true;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(d.ord));
+    std::vector<std::vector<Launch>> plans(end - first);
+    for (size_t k = first; k < end; k++) plans[k - first] = std::move(jobs[k].plan);
+    const Stage st(plans, rchunk);
+    const ScanJob job{kScanBatch};
+    std::vector<unsigned int> grids;
+    int rc = stage_upload(d, st, job, grids);
+    if (!rc) rc = arm_and_launch(d, st, job, 0, grids);
+    if (!rc) rc = read_back(d, st, job, index0 + first, index0 + end - 1);
+    return rc ? rc : decode(d, job, st);
 }
 
 // One ABI call: its device runs, batch by batch, and its statistics and launch records, which
@@ -412,22 +470,30 @@ struct Call {
     // host thread of its own.  Takes the entries' records and times; returns the first failure.
     int run(const uint8_t* msg, size_t msg_len, uint32_t rchunk, const std::vector<SubRange>& batch,
             const ScanJob& job) {
-        for (auto& d : ctx->devs) d.reset();
-        auto one = [&](const SubRange& s) {  // nothing may escape a std::thread (std::terminate)
+        return run_each(batch.size(), [&](size_t k) {  // nothing may escape a std::thread (std::terminate)
+            const SubRange& s = batch[k];
             Dev& d = ctx->devs[(size_t)s.shard];
             d.rc = guarded([&] { return dev_run(d, msg, msg_len, s.lo, s.hi, rchunk, ctx->policy, job); });
-        };
-        if (batch.size() == 1) {
-            one(batch[0]);
+        });
+    }
+
+    // Runs one(k) for k < n, each a device run on a context entry of its own that leaves its
+    // return code in that entry's rc: on the caller's thread when n is 1, else each on a host
+    // thread of its own.
+    template <class F>
+    int run_each(size_t n, F&& one) {
+        for (auto& d : ctx->devs) d.reset();
+        if (n == 1) {
+            one((size_t)0);
         } else {
             std::vector<std::thread> th;
-            th.reserve(batch.size());
+            th.reserve(n);
             // Thread creation can fail (std::system_error): the shards already started are
             // joined before the error is returned, so no joinable std::thread is destroyed.
             int spawn_rc = GPUHASH_OK;
-            for (size_t k = 0; k < batch.size() && spawn_rc == GPUHASH_OK; k++)
+            for (size_t k = 0; k < n && spawn_rc == GPUHASH_OK; k++)
                 spawn_rc = guarded([&] {
-                    th.emplace_back([&, k] { one(batch[k]); });
+                    th.emplace_back([&, k] { one(k); });
                     return GPUHASH_OK;
                 });
             for (auto& t : th) t.join();
@@ -452,7 +518,11 @@ struct Call {
     // The call examined the nonces [first, last].
     void finish(uint64_t first, uint64_t last) {
         const uint64_t span = last - first;
-        st.nonces = span == ~0ull ? ~0ull : span + 1;
+        finish_nonces(span == ~0ull ? ~0ull : span + 1);
+    }
+
+    void finish_nonces(uint64_t nonces) {
+        st.nonces = nonces;
         st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         ctx->last = st;
     }
@@ -670,6 +740,68 @@ int gpuhash_collect_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, 
                                     out_total);
 }
 
+// gpuhash_min_batch_ex, its arguments checked: the sub-batches (stage.h, for_each_sub_batch),
+// each cut into one run per context entry, which run concurrently.
+static int min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                     const uint64_t* lower, const uint64_t* upper, uint32_t rchunk, uint64_t* out_hashes,
+                     uint64_t* out_nonces) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Call call(ctx);
+    std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
+    const int policy = ctx->policy;
+    auto plan = [&](size_t k) {
+        const size_t len = msg_off[k + 1] - msg_off[k];
+        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
+        const std::vector<std::pair<size_t, size_t>> runs = batch_runs(jobs, ctx->devs.size());
+        const int rc = call.run_each(runs.size(), [&](size_t r) {
+            Dev& d = ctx->devs[r];
+            d.rc = guarded([&] { return dev_run_batch(d, jobs, runs[r].first, runs[r].second, first, rchunk); });
+        });
+        if (rc) return rc;
+        for (size_t r = 0; r < runs.size(); r++) {
+            const Dev& d = ctx->devs[r];
+            for (size_t k = runs[r].first; k < runs[r].second; k++) {
+                rh[first + k] = d.bat_h[k - runs[r].first];
+                rn[first + k] = d.bat_n[k - runs[r].first];
+            }
+        }
+        return GPUHASH_OK;
+    };
+    if (int rc = for_each_sub_batch(njobs, batch_bytes_bound(), plan, run)) return rc;
+    uint64_t nonces = 0;
+    for (size_t k = 0; k < njobs; k++) {
+        const uint64_t n = upper[k] - lower[k] + 1;  // <= GPUHASH_BATCH_MAX_SPAN
+        nonces = nonces + n < nonces ? ~0ull : nonces + n;
+    }
+    call.finish_nonces(nonces);
+    std::copy(rh.begin(), rh.end(), out_hashes);
+    std::copy(rn.begin(), rn.end(), out_nonces);
+    return GPUHASH_OK;
+}
+
+int gpuhash_min_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                         const uint64_t* lower, const uint64_t* upper, uint32_t rchunk, uint64_t* out_hashes,
+                         uint64_t* out_nonces) {
+    if (!ctx || !msg_off || !lower || !upper || !out_hashes || !out_nonces) return GPUHASH_EINVAL;
+    if (njobs == 0 || njobs > GPUHASH_BATCH_MAX_JOBS) return GPUHASH_EINVAL;
+    bool too_long = false;
+    for (size_t k = 0; k < njobs; k++) {
+        if (msg_off[k + 1] < msg_off[k] || lower[k] > upper[k]) return GPUHASH_EINVAL;
+        if (upper[k] - lower[k] >= GPUHASH_BATCH_MAX_SPAN) return GPUHASH_EINVAL;
+        too_long = too_long || msg_off[k + 1] - msg_off[k] > GPUHASH_MAX_MSG;
+    }
+    if (!msgs && msg_off[njobs] != msg_off[0]) return GPUHASH_EINVAL;
+    if (too_long) return GPUHASH_ETOOLONG;
+    return guarded([&] { return min_batch(ctx, msgs, msg_off, njobs, lower, upper, rchunk, out_hashes, out_nonces); });
+}
+
+int gpuhash_min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                      const uint64_t* lower, const uint64_t* upper, uint64_t* out_hashes, uint64_t* out_nonces) {
+    return gpuhash_min_batch_ex(ctx, msgs, msg_off, njobs, lower, upper, 0, out_hashes, out_nonces);
+}
+
 int gpuhash_min(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
                 uint64_t upper, uint64_t* out_hash, uint64_t* out_nonce) {
     return gpuhash_min_ex(ctx, msg, msg_len, lower, upper, 0, out_hash, out_nonce);
@@ -739,9 +871,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.5 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.6 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.5 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.6 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

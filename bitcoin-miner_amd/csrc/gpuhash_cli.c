@@ -14,9 +14,14 @@
  *                                         "Hit <hash> <nonce>" line for each of the lowest CAP
  *                                         (default GPUHASH_COLLECT_MAX) nonces whose hash is
  *                                         <= TARGET, ascending (gpuhash_collect_below)
+ *   gpuhash_cli --batch FILE           -> FILE holds one job per line, "MSG LOWER UPPER" (MSG
+ *                                         without blanks; empty lines are skipped); prints one
+ *                                         "Result <hash> <nonce>" per job, in order, from ONE
+ *                                         gpuhash_min_batch call ("-" reads standard input)
  *   gpuhash_cli --version
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
  */
+#define _POSIX_C_SOURCE 200809L /* getline, strtok_r */
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,17 +43,103 @@ static int fail(const char *what, int rc) {
     return 3;
 }
 
+/* --batch: every job of the file in one gpuhash_min_batch call. */
+static int batch_main(const char *path) {
+    FILE *f = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path);
+        return 2;
+    }
+    size_t njobs = 0, cap = 0, bytes = 0, bytes_cap = 0;
+    uint8_t *msgs = NULL;
+    size_t *off = NULL;
+    uint64_t *lower = NULL, *upper = NULL;
+    char *line = NULL;
+    size_t line_cap = 0;
+    int status = 0;
+    while (!status && getline(&line, &line_cap, f) >= 0) {
+        char *save = NULL;
+        const char *m = strtok_r(line, " \t\r\n", &save);
+        if (!m) continue; /* an empty line */
+        const char *lo = strtok_r(NULL, " \t\r\n", &save), *hi = strtok_r(NULL, " \t\r\n", &save);
+        uint64_t a, b;
+        if (!lo || !hi || strtok_r(NULL, " \t\r\n", &save) || parse_u64(lo, &a) || parse_u64(hi, &b)) {
+            fprintf(stderr, "line %zu: expected MSG LOWER UPPER\n", njobs + 1);
+            status = 2;
+            break;
+        }
+        const size_t len = strlen(m);
+        if (njobs == cap) {
+            cap = cap ? 2 * cap : 64;
+            off = (size_t *)realloc(off, (cap + 1) * sizeof *off);
+            lower = (uint64_t *)realloc(lower, cap * sizeof *lower);
+            upper = (uint64_t *)realloc(upper, cap * sizeof *upper);
+        }
+        if (bytes + len + 1 > bytes_cap) {
+            bytes_cap = 2 * (bytes + len + 1);
+            msgs = (uint8_t *)realloc(msgs, bytes_cap);
+        }
+        if (!off || !lower || !upper || !msgs) {
+            fprintf(stderr, "out of memory\n");
+            status = 3;
+            break;
+        }
+        memcpy(msgs + bytes, m, len);
+        off[njobs] = bytes;
+        bytes += len;
+        lower[njobs] = a;
+        upper[njobs] = b;
+        off[++njobs] = bytes;
+    }
+    free(line);
+    if (f != stdin) fclose(f);
+    uint64_t *h = NULL, *n = NULL;
+    if (!status && njobs == 0) {
+        fprintf(stderr, "no jobs in %s\n", path);
+        status = 2;
+    }
+    if (!status) {
+        h = (uint64_t *)malloc(njobs * sizeof *h);
+        n = (uint64_t *)malloc(njobs * sizeof *n);
+        gpuhash_ctx *ctx = NULL;
+        int rc = h && n ? gpuhash_open(NULL, 0, &ctx) : GPUHASH_ENOMEM;
+        if (rc) {
+            status = fail("gpuhash_open", rc);
+        } else {
+            rc = gpuhash_min_batch(ctx, msgs, off, njobs, lower, upper, h, n);
+            if (rc) status = fail("gpuhash_min_batch", rc);
+            for (size_t k = 0; k < njobs && !status; k++) {
+                if (gpuhash_hash_cpu(msgs + off[k], off[k + 1] - off[k], n[k]) != h[k] || n[k] < lower[k] ||
+                    n[k] > upper[k]) {
+                    fprintf(stderr, "self-check failed at job %zu: Hash(msg, %" PRIu64 ") != %" PRIu64 "\n", k, n[k], h[k]);
+                    status = 4;
+                }
+            }
+            for (size_t k = 0; k < njobs && !status; k++) printf("Result %" PRIu64 " %" PRIu64 "\n", h[k], n[k]);
+            gpuhash_close(ctx);
+        }
+    }
+    free(h);
+    free(n);
+    free(msgs);
+    free(off);
+    free(lower);
+    free(upper);
+    return status;
+}
+
 int main(int argc, char **argv) {
     if (argc == 2 && strcmp(argv[1], "--version") == 0) {
         printf("%s\n", gpuhash_version());
         return 0;
     }
+    if (argc == 3 && strcmp(argv[1], "--batch") == 0) return batch_main(argv[2]);
     const int range_mode = argc == 5 && strcmp(argv[1], "--range") == 0;
     const int below_mode = argc == 6 && strcmp(argv[1], "--below") == 0;
     const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
     if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --version\n", argv[0]);
         return 2;
     }
     const int opt = range_mode || below_mode || all_mode;

@@ -225,6 +225,16 @@ struct Staged {
 
     Staged(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy)
         : st(msg, len, lo, hi, rchunk, policy, /*host_ptab=*/true), meta(st.bytes) {
+        read_groups();
+    }
+
+    // A batch stage: plans[k] = job k's plan, with host p-tables.
+    Staged(std::vector<std::vector<Launch>>& plans, uint32_t rchunk) : st(plans, rchunk), meta(st.bytes) {
+        read_groups();
+    }
+
+   private:
+    void read_groups() {
         st.fill(meta.data());
         for (const StageGroup& sg : st.groups) {
             VGroup g;
@@ -476,6 +486,231 @@ int hostcheck_parts(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t u
         }
     }
     return n;
+}
+
+}  // extern "C"
+
+// ---- batch search (gpuhash_min_batch): CPU replay of the kernel's MODE 4 ----
+//
+// A batch stage's groups, pieces, parts and masks as k_scan<.., 4> walks them, from the bytes
+// fill() wrote: the descriptor lookup that resumes from the previous part (batch_find), the
+// job-change flush, the per-job pruning words and the result list with its bound.  A workgroup
+// is replayed with its four waves' running bests.  What a GPU decides by timing -- which
+// workgroup takes which piece, and what a workgroup reads in a pruning word before another has
+// flushed -- is chosen by a seed, within what the work counter allows: a workgroup's pieces are
+// ascending, since every grab returns a higher position than the one before.
+
+namespace {
+
+struct ReplayWave {
+    uint64_t h = ~0ull, n = ~0ull;
+    uint32_t T = 0xFFFFFFFFu;
+};
+
+struct ReplayWg {
+    std::vector<size_t> pieces;  // ascending
+    size_t next = 0;
+    ReplayWave w[4];
+    uint32_t job = 0xFFFFFFFFu;  // kNoJob
+    int idx = 0;                 // batch_find's hint
+};
+
+// One run of a batch on one context entry; appends to nothing outside it.
+struct BatchReplay {
+    const Staged& run;
+    std::vector<uint64_t> thresh;
+    std::vector<BatchEntry> list;
+    Rng* jitter = nullptr;
+
+    explicit BatchReplay(const Staged& r) : run(r), thresh(r.st.njobs) {
+        std::memcpy(thresh.data(), r.meta.data() + r.st.thresh_at, 8 * r.st.njobs);  // as fill() armed them
+    }
+
+    void flush(ReplayWg& wg) {
+        uint64_t bh = wg.w[0].h, bn = wg.w[0].n;
+        for (int i = 1; i < 4; i++)
+            if (wg.w[i].h < bh || (wg.w[i].h == bh && wg.w[i].n < bn)) { bh = wg.w[i].h; bn = wg.w[i].n; }
+        if (bh != ~0ull || bn != ~0ull) {
+            thresh[wg.job] = std::min(thresh[wg.job], bh);
+            list.push_back(BatchEntry{bh, bn, wg.job, 0});
+        }
+    }
+
+    // The kernel's batch_find: the largest i with offs[i] <= x, from a hint that is any index.
+    static int find(const VGroup& g, int i, uint64_t x) {
+        const int ndesc = (int)g.ls.size();
+        int lo = 0, hi = ndesc - 1;
+        if (g.offs[i] > x) {
+            hi = i - 1;
+        } else if (i + 1 < ndesc && g.offs[i + 1] <= x) {
+            i++;
+            if (i + 1 < ndesc && g.offs[i + 1] <= x) lo = i + 1;
+            else lo = hi = i;
+        } else {
+            return i;
+        }
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (g.offs[mid] <= x) lo = mid;
+            else hi = mid - 1;
+        }
+        return lo;
+    }
+
+    void piece(const VGroup& g, ReplayWg& wg, uint64_t x, uint64_t end) {
+        if (wg.job != 0xFFFFFFFFu)  // the grab: tighten T from the current job's word
+            for (ReplayWave& w : wg.w) w.T = std::min(w.T, (uint32_t)(thresh[wg.job] >> 32));
+        while (x < end) {
+            // the hint is whatever descriptor some wave of the workgroup found last: under a
+            // shuffle, now and then any index at all
+            if (jitter && jitter->next() % 4 == 0) wg.idx = (int)(jitter->next() % g.ls.size());
+            const int i = wg.idx = find(g, wg.idx, x);
+            const LaunchDesc& D = g.descs[i];
+            const uint32_t rel = (uint32_t)(x - g.offs[i]);
+            const uint32_t row = rel / D.R, r0 = rel - row * D.R;
+            const uint64_t left = end - x;
+            const uint32_t r1 = (uint64_t)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
+            if (D.job != wg.job) {
+                if (wg.job != 0xFFFFFFFFu) flush(wg);
+                wg.job = D.job;
+                for (ReplayWave& w : wg.w) w = ReplayWave{~0ull, ~0ull, (uint32_t)(thresh[D.job] >> 32)};
+            }
+            const Part pt{g.ls[(size_t)i], &D, row, r0, r1, x, g.offs[i + 1]};
+            for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                ReplayWave& w = wg.w[((p - D.p_first) & 255u) >> 6];
+                const uint64_t h = replay_hash(*pt.l, p, r);
+                const uint32_t h0 = (uint32_t)(h >> 32);
+                if (h0 > w.T) return;  // the prune: H0 <= wb.T takes the slow path
+                if (h < w.h || (h == w.h && n < w.n)) {
+                    w.h = h;
+                    w.n = n;
+                    w.T = std::min(w.T, h0);
+                }
+            });
+            x += r1 - r0;
+        }
+    }
+
+    void group(size_t gi, uint64_t order_seed, Rng& rng) {
+        const VGroup& g = run.groups[gi];
+        const size_t np = g.pieces.size();
+        jitter = order_seed > 1 ? &rng : nullptr;
+        const size_t grid = Stage::grid(run.st.groups[gi], std::min<unsigned int>(kReplayGrid, kBatchMaxGrid));
+        // seed 0: one workgroup takes every piece, ascending.  seed 1: as many workgroups as the
+        // grid allows take contiguous shares and run one after the other, the LAST share first
+        // (strictly descending pieces when there is a workgroup per piece).  Else 2-8 workgroups
+        // in flight, each piece dealt to a random one, and the next piece to run picked at
+        // random among the workgroups' next ones.
+        const size_t W = order_seed == 0 ? 1 : order_seed == 1 ? std::min(grid, np)
+                                                               : std::min({grid, np, (size_t)(2 + rng.next() % 7)});
+        std::vector<ReplayWg> wgs(W);
+        for (size_t k = 0; k < np; k++) {
+            const size_t w = order_seed == 0 ? 0 : order_seed == 1 ? k * W / np : rng.next() % W;
+            wgs[w].pieces.push_back(k);
+        }
+        auto step = [&](ReplayWg& wg) {
+            const auto& pc = g.pieces[wg.pieces[wg.next++]];
+            piece(g, wg, pc.first, pc.second);
+            if (wg.next == wg.pieces.size() && wg.job != 0xFFFFFFFFu) flush(wg);  // the end of the kernel
+        };
+        if (order_seed <= 1) {
+            for (size_t w = W; w-- > 0;)
+                while (wgs[w].next < wgs[w].pieces.size()) step(wgs[w]);
+            return;
+        }
+        std::vector<size_t> live;
+        for (size_t w = 0; w < W; w++)
+            if (!wgs[w].pieces.empty()) live.push_back(w);
+        while (!live.empty()) {
+            const size_t at = rng.next() % live.size();
+            ReplayWg& wg = wgs[live[at]];
+            step(wg);
+            if (wg.next == wg.pieces.size()) live.erase(live.begin() + (long)at);
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// gpuhash_min_batch as the engine runs it: the same sub-batches (for_each_sub_batch under
+// batch_bytes, 0: the engine's bound), runs over nshards context entries (batch_runs) and batch
+// stages, each run replayed as above with the order of its pieces chosen by order_seed (0, 1 or
+// a shuffle, see BatchReplay::group).  msg_off has njobs + 1 entries.  Returns 0 and the per-job
+// results, and in out_fill[0..3]: the largest result-list fill of any run, that run's bound
+// (Stage::list_cap), how many runs filled their list past its bound (0, or the bound is wrong),
+// and the number of sub-batches.
+int hostcheck_min_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs, const uint64_t* lower,
+                        const uint64_t* upper, uint32_t rchunk, int policy, uint64_t order_seed,
+                        uint64_t batch_bytes, int nshards, uint64_t* out_hashes, uint64_t* out_nonces,
+                        uint64_t* out_fill) {
+    if (!msg_off || !lower || !upper || !out_hashes || !out_nonces || !out_fill || !njobs || nshards < 1) return -1;
+    for (uint64_t k = 0; k < njobs; k++)
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+    Rng rng{order_seed};
+    uint64_t fill[4] = {0, 0, 0, 0};
+    auto plan = [&](size_t k) {
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy,
+                        /*host_ptab=*/true);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
+        fill[3]++;
+        for (const auto& r : batch_runs(jobs, (size_t)nshards)) {
+            std::vector<std::vector<Launch>> plans(r.second - r.first);
+            for (size_t k = r.first; k < r.second; k++) plans[k - r.first] = std::move(jobs[k].plan);
+            const Staged staged(plans, rchunk);
+            BatchReplay rep(staged);
+            for (size_t gi = 0; gi < staged.groups.size(); gi++) rep.group(gi, order_seed, rng);
+            if (rep.list.size() >= fill[0]) { fill[0] = rep.list.size(); fill[1] = staged.st.list_cap; }
+            fill[2] += rep.list.size() > staged.st.list_cap ? 1 : 0;
+            for (size_t k = r.first; k < r.second; k++) out_hashes[first + k] = out_nonces[first + k] = ~0ull;
+            for (const BatchEntry& e : rep.list) {  // the host's fold
+                uint64_t &h = out_hashes[first + r.first + e.job], &n = out_nonces[first + r.first + e.job];
+                if (e.hash < h || (e.hash == h && e.nonce < n)) { h = e.hash; n = e.nonce; }
+            }
+        }
+        return 0;
+    };
+    if (int rc = for_each_sub_batch((size_t)njobs, batch_bytes_bound(batch_bytes), plan, run)) return rc;
+    std::memcpy(out_fill, fill, sizeof fill);
+    return 0;
+}
+
+// The stage of ONE run of a batch (all njobs jobs on one context entry, no sub-batch cut) under
+// hostcheck_set_layout_policy's policy, as hostcheck_stage gives a single search's: the same 14
+// words per variant group, *bytes and meta, and in extra[0..7] the bytes the host uploads, the
+// byte position and size of the per-job pruning words, the byte position of the result list
+// (its 16-byte head first) and its capacity in entries, the size of an entry, and the number
+// of K+W tables and their words in all.
+int hostcheck_stage_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs, const uint64_t* lower,
+                          const uint64_t* upper, uint32_t rchunk, uint64_t* out, int cap, uint64_t* bytes,
+                          uint64_t* extra, uint8_t* meta, uint64_t meta_cap) {
+    if (!msg_off || !lower || !upper || !bytes || !extra || !njobs) return -1;
+    std::vector<std::vector<Launch>> plans(njobs);
+    for (uint64_t k = 0; k < njobs; k++) {
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        plan_range(len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k], plans[k], rchunk, g_policy);
+    }
+    const Stage st(plans, rchunk);
+    for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
+        const StageGroup& g = st.groups[(size_t)i];
+        const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,
+                                  (uint64_t)g.c, g.total, g.nonces, g.work_at, g.offs_at, g.desc_at, g.ptab_at,
+                                  sizeof(LaunchDesc) * g.idx.size(), g.ptab_bytes};
+        std::memcpy(out + 14 * i, row, sizeof row);
+    }
+    *bytes = st.bytes;
+    const uint64_t ex[8] = {st.upload_bytes, st.thresh_at, 8 * st.njobs, st.list_at, st.list_cap,
+                            sizeof(BatchEntry), st.tabs.size(), st.tab_words};
+    std::memcpy(extra, ex, sizeof ex);
+    if (meta && meta_cap >= st.bytes) {
+        std::memset(meta, 0, st.bytes);
+        st.fill(meta);
+    }
+    return (int)st.groups.size();
 }
 
 }  // extern "C"

@@ -25,7 +25,9 @@ struct ScanArgs {
                                      // s_memrealtime of workgroup 0 at its start and its end
     unsigned int gmin, gmax;         // piece size bounds (r values per grab; stage.h)
     unsigned long long* thresh;      // the shared 64-bit word: a bound or the hit counter
-    Cand* cands;                     // appended candidates, or the hit list
+                                     // (batch: one pruning word per job)
+    Cand* cands;                     // appended candidates, or the hit list (batch: the result
+                                     // list, BatchEntry)
     unsigned int* ncand;             // append counter, or the hit list's capacity
     unsigned long long* dump;        // MODE 1 only: per-nonce hashes
     unsigned long long dump_lo;      // nonce of dump[0], or the target
@@ -34,14 +36,15 @@ struct ScanArgs {
 };
 
 // The scan kernels' MODE template parameter (scan_kernel.h), by name on the host.
-enum ScanMode : int { kScanMin = 0, kScanDump = 1, kScanFirst = 2, kScanCollect = 3 };
+enum ScanMode : int { kScanMin = 0, kScanDump = 1, kScanFirst = 2, kScanCollect = 3, kScanBatch = 4 };
 
 // Resident workgroups of 256 threads for the (J, C2, EX, mode) kernel on this device.
 unsigned int grid_for(int J, int C2, int EX, int mode, int device);
 
 // One persistent launch of the (J, C2, EX) variant over a.descs[0..ndesc).  mode 0: argmin
 // search, 1: per-nonce dump, 2: first hit at or below a target (gpuhash_first_below), 3: every
-// hit at or below a target, counted and listed (gpuhash_collect_below).
+// hit at or below a target, counted and listed (gpuhash_collect_below), 4: the argmin search of
+// every job of a batch (gpuhash_min_batch).
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a);
 // Fills the uniform K+W table of a C2/J=0 descriptor: tab[64*r + t] = K[t] + W_t(r),
 // r in [0, D.R), for block B's words U with the loop digits of r inserted into W_0.

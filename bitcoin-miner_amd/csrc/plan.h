@@ -83,7 +83,16 @@ struct LaunchDesc {
     // last digit, nonce = k·stride + tail; plain launches: stride 1, tail 0
     uint32_t stride;
     uint32_t tail;
-    uint32_t pad2_;
+    // the job of a batch this descriptor belongs to (gpuhash_min_batch, stage.h): the index of
+    // its pruning word and the tag of its result-list entries.  0 in a single-job stage.
+    uint32_t job;
+};
+
+// One entry of a batch's result list (gpuhash_min_batch), as the scan kernel's MODE 4 appends
+// it: the best (hash, nonce) a workgroup held for job `job` when it left that job.
+struct BatchEntry {
+    unsigned long long hash, nonce;
+    uint32_t job, pad_;
 };
 
 #ifdef __HIPCC__

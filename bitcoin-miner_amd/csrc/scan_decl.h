@@ -8,7 +8,8 @@
 //   kernels_misc.hip   C2 = 1/J = 1, C2 = 2, extra-block layouts: max-ILP scheduling
 // The first-hit instances (MODE 2) of each family are in kernels_{plain,ut,misc}_first.hip,
 // built with that family's options, and the collecting instances (MODE 3) likewise in
-// kernels_{plain,ut,misc}_collect.hip.
+// kernels_{plain,ut,misc}_collect.hip, and the batch instances (MODE 4) in
+// kernels_{plain,ut,misc}_batch.hip.
 // kernels.hip launches them through these declarations only, so nothing is implicitly
 // instantiated there.
 #pragma once

@@ -34,6 +34,10 @@
 // per-nonce compare and ballot; the slow path appends.  Its instances live in
 // kernels_*_collect.hip, and MODE 0, 1 and 2 compile to the same machine code with or
 // without it.
+//
+// MODE 4 is MODE 0 for a batch of independent jobs, gpuhash_min_batch (BatchState, below).  Its
+// instances live in kernels_*_batch.hip, and the other modes compile to the same machine code
+// with or without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -268,6 +272,115 @@ __device__ __forceinline__ void collect_store(unsigned long long slot, unsigned 
         e->hash = hh;
         e->nonce = nn;
     }
+}
+
+// MODE 4 (batch, gpuhash_min_batch): MODE 0's question for many independent jobs in one launch.
+// Every descriptor names its job (LaunchDesc::job) and a group's descriptors lie in ascending
+// job order.  Per nonce nothing differs from MODE 0: the compare of H0 against wb.T, the ballot
+// and MODE 0's slow path.  What is per launch in MODE 0 is per job here, and k_scan's arguments
+// are reused:
+//   thresh   an array of pruning words, one per job (armed to all ones): thresh[job] only ever
+//            holds a hash some nonce of that job achieved
+//   cands    the result list, BatchEntry{hash, nonce, job}
+//   ncand    the list's append counter (armed to 0); the word after it is the list's capacity
+// A workgroup's WaveBest belongs to one job at a time.  When the next part's descriptor names
+// another job the workgroup FLUSHES -- merges its four waves through LDS, lowers thresh[job]
+// and appends one entry, if it holds a candidate at all -- and re-arms wb from the new job's
+// word; it flushes once more at the end of the kernel.  Parts, pieces and descriptor order are
+// workgroup-uniform, so the flush's barriers are met by all four waves (between rows, never
+// inside one).  The host folds the list per job by the (hash, nonce) key: the wave that hashes
+// a job's argmin keeps it (T never falls below the high word of a hash of that job, and ties
+// take the slow path), its workgroup appends it, and the fold finds it.  No workgroup waits on
+// another.  The capacity is a proved bound (stage.h, batch_job_entries); the store is guarded
+// by it all the same.
+// The mode's words live in LDS and come back to scalar registers on these cold paths only, so
+// nothing but MODE 0's WaveBest is live across the per-nonce loop.
+constexpr uint32_t kNoJob = 0xFFFFFFFFu;
+struct BatchState {
+    unsigned long long* thresh;
+    BatchEntry* list;
+    unsigned int* count;
+    // The job the workgroup's WaveBest belongs to (kNoJob: none yet).  Thread 0 writes it at a
+    // job change, between two barriers: every wave has read the old value before, and reads
+    // the new one after.  One word for the workgroup, at a constant LDS address: a slot per
+    // wave, indexed by threadIdx.x >> 6, kept that index alive in a VGPR across the per-nonce
+    // loop, and the plain kernels have none to spare (one K+W sum then moved into the loop).
+    uint32_t job;
+    // A HINT for the next descriptor lookup: the descriptor some wave found last.  The waves
+    // write it unsynchronised (they find the same descriptors, but not at the same time), so
+    // batch_find trusts no more of it than that it is an index.
+    uint32_t idx;
+};
+__device__ __forceinline__ BatchState& batch_state() {
+    __shared__ BatchState bs;
+    return bs;
+}
+
+// The pruning word of `job`, its high half: the T to arm or tighten a WaveBest with.
+__device__ __forceinline__ uint32_t batch_T(uint32_t job) {
+    unsigned long long* const th = (unsigned long long*)uniform64((unsigned long long)batch_state().thresh);
+    const unsigned long long tv = __hip_atomic_load(th + job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return __builtin_amdgcn_readfirstlane((uint32_t)(tv >> 32));
+}
+
+// Leaves `job`: the workgroup's best for it, one list entry if it has any.  Every wave of the
+// workgroup calls this at the same point.
+__device__ __forceinline__ void batch_flush(const WaveBest& wb, uint32_t job,
+                                            unsigned long long (&sh_best)[4][2]) {
+    const uint32_t tid = threadIdx.x;
+    if ((tid & 63u) == 0) { sh_best[tid >> 6][0] = wb.h; sh_best[tid >> 6][1] = wb.n; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long bh = sh_best[0][0], bn = sh_best[0][1];
+#pragma unroll
+        for (int i = 1; i < 4; i++) {
+            if (sh_best[i][0] < bh || (sh_best[i][0] == bh && sh_best[i][1] < bn)) {
+                bh = sh_best[i][0];
+                bn = sh_best[i][1];
+            }
+        }
+        if (bh != ~0ull || bn != ~0ull) {
+            BatchState& bs = batch_state();
+            atomicMin(bs.thresh + job, bh);
+            const unsigned int idx = atomicAdd(bs.count, 1u);
+            if (idx < bs.count[1]) {
+                BatchEntry* const e = bs.list + idx;
+                e->hash = bh;
+                e->nonce = bn;
+                e->job = job;
+            }
+        }
+    }
+    __syncthreads();  // sh_best is free again
+}
+
+// The descriptor that owns position x: the largest i with offs[i] <= x (offs[0] = 0 and the
+// offsets rise strictly).  A workgroup's positions only rise, so the search starts from the
+// hint, the descriptor of a previous part: usually it is that one or the next, else a binary
+// search of the descriptors after it -- or before it, if the hint came from a wave that is
+// already further on.  O(log ndesc) scalar loads at worst, two at best.
+__device__ __forceinline__ int batch_find(const unsigned long long* __restrict__ offs, int ndesc,
+                                          unsigned long long x) {
+    BatchState& bs = batch_state();
+    int i = (int)__builtin_amdgcn_readfirstlane(bs.idx);
+    int lo = 0, hi = ndesc - 1;
+    if (offs[i] > x) {
+        hi = i - 1;
+    } else if (i + 1 < ndesc && offs[i + 1] <= x) {
+        i++;
+        if (i + 1 < ndesc && offs[i + 1] <= x) lo = i + 1;
+        else lo = hi = i;
+    } else {
+        return i;
+    }
+    while (lo < hi) {  // offs[lo] <= x
+        const int mid = (lo + hi + 1) >> 1;
+        if (offs[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    i = lo;
+    if ((threadIdx.x & 63u) == 0) bs.idx = (uint32_t)i;
+    return i;
 }
 
 // Rounds 0..63 of block B when its whole message schedule is wave-uniform (C2 layouts
@@ -728,6 +841,16 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         }
         __syncthreads();
     }
+    if constexpr (MODE == 4) {  // thresh, cands, ncand: see BatchState
+        BatchState& bs = batch_state();
+        if (tid == 0) {
+            bs.thresh = thresh;
+            bs.list = reinterpret_cast<BatchEntry*>(cands);
+            bs.count = ncand;
+        }
+        if (tid == 0) { bs.job = kNoJob; bs.idx = 0u; }
+        __syncthreads();
+    }
     for (;;) {
         if (tid == 0) {
             const unsigned long long cur = __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -752,6 +875,13 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)(tv >> 32));
             wb.T = t < wb.T ? t : wb.T;
         }
+        if constexpr (MODE == 4) {  // the same, from the word of the job the workgroup is in
+            const uint32_t cur = __builtin_amdgcn_readfirstlane(batch_state().job);
+            if (cur != kNoJob) {
+                const uint32_t t = batch_T(cur);
+                wb.T = t < wb.T ? t : wb.T;
+            }
+        }
         // MODE 2: `thresh` holds the lowest qualifying nonce found so far by any workgroup
         // (all ones: none yet).  Thread 0 read it once, at the grab, and every wave took
         // that one value between the grab's two barriers: the skip decisions below MUST be
@@ -774,9 +904,29 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         }
         while (x < end) {
             int i = 0;
-            while (i + 1 < ndesc && offs[i + 1] <= x) i++;
+            if constexpr (MODE == 4) {  // thousands of descriptors per group: no linear walk
+                i = batch_find(offs, ndesc, x);
+                // held as a scalar from here on: without this LLVM moves part of the loop's
+                // uniform ascii4(r) onto the VALU (+4 VALU instructions per nonce at J = 4)
+                asm volatile("" : "+s"(i));
+            } else {
+                while (i + 1 < ndesc && offs[i + 1] <= x) i++;
+            }
             const LaunchDesc& D = descs[i];
             const uint32_t rel = (uint32_t)(x - offs[i]);  // < rows * R <= 2^32 (plan.h)
+            if constexpr (MODE == 4) {
+                // a part of another job: leave the current one, re-arm from the new job's word
+                BatchState& bs = batch_state();
+                const uint32_t job = __builtin_amdgcn_readfirstlane(D.job);
+                const uint32_t cur = __builtin_amdgcn_readfirstlane(bs.job);
+                if (job != cur) {
+                    if (cur != kNoJob) batch_flush(wb, cur, sh_best);
+                    else __syncthreads();
+                    if (tid == 0) bs.job = job;
+                    __syncthreads();
+                    wb = WaveBest{~0ull, ~0ull, batch_T(job)};
+                }
+            }
             const uint32_t row = rel / D.R, r0 = rel - row * D.R;
             const unsigned long long left = end - x;
             const uint32_t r1 = (unsigned long long)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
@@ -834,6 +984,10 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                 cands[idx].nonce = bn;
             }
         }
+    }
+    if constexpr (MODE == 4) {  // leave the last job
+        const uint32_t cur = __builtin_amdgcn_readfirstlane(batch_state().job);
+        if (cur != kNoJob) batch_flush(wb, cur, sh_best);
     }
     if constexpr (MODE == 2) {
         // the workgroup's lowest-nonce hit, appended only if it has one (the host reads

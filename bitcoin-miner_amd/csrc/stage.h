@@ -70,12 +70,148 @@ struct StageGroup {
 
 // A uniform K+W table of C2 = 1 / J = 0 descriptors: block B's words depend only on the digit
 // count d, so one table of 64 x R words per d serves all of them; k_ktab builds it from the
-// device copy of the first such descriptor, at desc_byte.
+// device copy of the first such descriptor, at desc_byte.  (A batch stage has many messages:
+// there a table serves the descriptors whose block B words U and R equal that descriptor's.)
 struct StageTab {
     int d;
     uint32_t off, R;  // words
     size_t desc_byte;
+    size_t launch = 0;  // that descriptor's launch in Stage::plan
 };
+
+// One search of a batch (gpuhash_min_batch).
+struct BatchJob {
+    const uint8_t* msg;
+    uint64_t len, lo, hi;
+};
+
+// the list's head: its append counter and its capacity in entries (a uint32 each), padding
+constexpr size_t kBatchListHead = 16;
+
+// A batch launch never has more workgroups than this, whatever the device holds resident
+// (an MI355X holds 2048 of the plain kernels'), so the list bound below needs no device.
+constexpr uint32_t kBatchMaxGrid = 4096;
+
+// The most entries the workgroups of a launch of <= grid workgroups can append for a job whose
+// descriptors cover `span` consecutive row-iterations.  A workgroup's grabs return ascending
+// positions (the work counter only rises) and a group's jobs lie in ascending order of
+// position, so a workgroup meets each job in one unbroken run of its parts and leaves it once:
+// at most one entry per workgroup that took a piece overlapping the job.  Pieces are disjoint
+// and consecutive, each at least gmin long except the last of the group, so at most
+// ceil(span / gmin) + 1 of them overlap `span` positions.
+inline uint64_t batch_job_entries(uint64_t span, uint32_t gmin, uint64_t grid) {
+    return std::min<uint64_t>(grid, (span + gmin - 1) / gmin + 1);
+}
+
+// The metadata bytes a job adds to a batch stage, at most (every alignment gap at its widest):
+// what the sub-batch cut (gpuhash.h) sums, with the K+W tables the job adds (BatchTables).
+inline uint64_t batch_job_bytes(const std::vector<Launch>& plan, uint32_t gmin) {
+    uint64_t b = 8 + 16;  // its pruning word; its share of the list head
+    for (const Launch& l : plan) {
+        b += sizeof(LaunchDesc) + 8 + kCounterBytes + 4 * 16;
+        b += sizeof(uint32_t) * l.nptab;
+        b += sizeof(BatchEntry) * batch_job_entries(row_iterations(l.desc), gmin, kBatchMaxGrid);
+    }
+    return b;
+}
+
+// The K+W tables of the jobs taken into a sub-batch so far, by what a table is computed from
+// (block B's uniform words and R, as Stage shares them).
+struct BatchTables {
+    std::vector<const LaunchDesc*> keys;
+
+    static bool same(const LaunchDesc& a, const LaunchDesc& b) {
+        return a.R == b.R && !std::memcmp(a.U, b.U, sizeof a.U);
+    }
+    // Bytes of the tables `plan` needs that are not held yet; take = true holds them.  The
+    // descriptors must stay where they are while the sub-batch is being cut.
+    uint64_t add(const std::vector<Launch>& plan, bool take) {
+        uint64_t bytes = 0;
+        const size_t held = keys.size();
+        for (const Launch& l : plan) {
+            if (l.C2 != 1 || l.J != 0) continue;
+            if (std::any_of(keys.begin(), keys.end(), [&](const LaunchDesc* k) { return same(*k, l.desc); })) continue;
+            keys.push_back(&l.desc);
+            bytes += 4 * 64ull * l.desc.R;
+        }
+        if (!take) keys.resize(held);
+        return bytes;
+    }
+};
+
+// A job of a batch, planned: its launches, batch_job_bytes of them and their plan_cost.
+struct PlannedJob {
+    std::vector<Launch> plan;
+    uint64_t bytes;
+    double cost;
+};
+
+inline PlannedJob plan_job(const BatchJob& j, uint32_t rchunk, int policy, bool host_ptab = false) {
+    PlannedJob p;
+    plan_range(j.msg, j.len, j.lo, j.hi, p.plan, rchunk, policy, host_ptab);
+    const uint32_t gmax = rchunk ? rchunk : kDefaultMaxPiece;
+    p.bytes = batch_job_bytes(p.plan, std::min(kMinPiece, gmax));
+    p.cost = plan_cost(p.plan);
+    return p;
+}
+
+// The bound on a sub-batch's metadata and table bytes (include/gpuhash.h, gpuhash_min_batch):
+// GPUHASH_BATCH_BYTES, or `bytes`, overrides the default; at most 1 GiB, so that a list's
+// entry count fits its 32-bit head.
+inline uint64_t batch_bytes_bound(uint64_t bytes = 0) {
+    if (!bytes) bytes = env_u64("GPUHASH_BATCH_BYTES");
+    if (!bytes) bytes = GPUHASH_BATCH_BYTES_DEFAULT;
+    return std::min<uint64_t>(bytes, 1ull << 30);
+}
+
+// Walks a batch of njobs jobs as consecutive sub-batches of whole jobs: jobs are planned one
+// by one (plan(k) -> PlannedJob) and a sub-batch ends before the job that would take the sum
+// of its jobs' batch_job_bytes and of their K+W tables, shared ones counted once, past `bound`; a sub-batch always holds at least one job.
+// run(first, jobs) runs the sub-batch whose first job is `first`; a non-zero return ends the walk.
+template <class Plan, class Run>
+int for_each_sub_batch(size_t njobs, uint64_t bound, Plan&& plan, Run&& run) {
+    std::vector<PlannedJob> jobs;
+    PlannedJob held;
+    bool holding = false;
+    for (size_t first = 0, k = 0; first < njobs; first = k) {
+        jobs.clear();
+        jobs.reserve(njobs - first);  // the table keys point into the jobs' plans: no moves
+        BatchTables tabs;
+        uint64_t sum = 0;
+        for (; k < njobs; k++) {
+            PlannedJob p = holding ? std::move(held) : plan(k);
+            holding = false;
+            if (!jobs.empty() && sum + p.bytes + tabs.add(p.plan, false) > bound) {
+                held = std::move(p);
+                holding = true;
+                break;
+            }
+            jobs.push_back(std::move(p));
+            sum += jobs.back().bytes + tabs.add(jobs.back().plan, true);
+        }
+        if (int rc = run(first, jobs)) return rc;
+    }
+    return 0;
+}
+
+// A sub-batch's jobs as at most n contiguous runs of about equal plan_cost, one per context
+// entry, [first, end) each; a job is never split.
+inline std::vector<std::pair<size_t, size_t>> batch_runs(const std::vector<PlannedJob>& jobs, size_t n) {
+    std::vector<std::pair<size_t, size_t>> runs;
+    double total = 0, acc = 0;
+    for (const PlannedJob& j : jobs) total += j.cost;
+    size_t start = 0, r = 0;
+    for (size_t k = 0; k < jobs.size(); k++) {
+        acc += jobs[k].cost;
+        const bool last = k + 1 == jobs.size();
+        if (last || (runs.size() + 1 < n && acc >= total * (double)(r + 1) / (double)n)) {
+            runs.push_back({start, k + 1});
+            start = k + 1;
+            r = std::max(r + 1, total > 0 ? (size_t)(acc * (double)n / total) : r + 1);
+        }
+    }
+    return runs;
+}
 
 struct Stage {
     std::vector<Launch> plan;  // desc.tab_off set as the kernels read it
@@ -83,10 +219,36 @@ struct Stage {
     std::vector<StageTab> tabs;
     size_t tab_words = 0, bytes = 0;  // of all K+W tables; of the metadata buffer
     uint32_t gmax, gmin;              // piece size bounds
+    // A batch stage (njobs > 0): desc.job of every launch is its job's index, a group's
+    // launches are in ascending job order, and after the groups' regions the buffer holds
+    // njobs pruning words (8 B each, armed to all ones) at thresh_at and the result list at
+    // list_at: kBatchListHead bytes of append counter, then room for list_cap BatchEntry.
+    // Only the first upload_bytes bytes are host-built (a single stage: all of them).
+    size_t njobs = 0, thresh_at = 0, list_at = 0, list_cap = 0, upload_bytes = 0;
 
     Stage(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy,
           bool host_ptab = false) : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)) {
         plan_range(msg, len, lo, hi, plan, rchunk, policy, host_ptab);
+        lay_out();
+    }
+
+    // The stage of a batch: plans[k] is job k's plan_range under the context's policy (moved
+    // from).  All launches of all jobs are grouped by (J, C2, EX) in first-appearance order;
+    // within a group each job's descriptors are contiguous, jobs ascending.
+    Stage(std::vector<std::vector<Launch>>& plans, uint32_t rchunk)
+        : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()) {
+        for (size_t k = 0; k < plans.size(); k++)
+            for (Launch& l : plans[k]) {
+                l.desc.job = (uint32_t)k;
+                plan.push_back(std::move(l));
+            }
+        lay_out();
+    }
+
+    static size_t aligned(size_t b) { return (b + 15) & ~(size_t)15; }
+
+   private:
+    void lay_out() {
         for (size_t i = 0; i < plan.size(); i++) {
             const Launch& l = plan[i];
             auto it = std::find_if(groups.begin(), groups.end(), [&](const StageGroup& g) {
@@ -95,7 +257,7 @@ struct Stage {
             if (it == groups.end()) it = groups.insert(it, StageGroup{l.J, l.C2, l.EX});
             it->idx.push_back(i);
         }
-        auto align = [&] { bytes = (bytes + 15) & ~(size_t)15; };
+        auto align = [&] { bytes = aligned(bytes); };
         bytes = kCounterBytes * groups.size();
         align();
         for (size_t gi = 0; gi < groups.size(); gi++) {
@@ -121,10 +283,17 @@ struct Stage {
                     g.ptab_bytes += sizeof(uint32_t) * l.nptab;
                 }
                 if (l.C2 == 1 && l.J == 0) {
-                    auto it = std::find_if(tabs.begin(), tabs.end(), [&](const StageTab& t) { return t.d == l.d; });
+                    // one message: block B's words follow from d.  A batch: the table is keyed
+                    // by what it is computed from, block B's uniform words and R, so jobs that
+                    // agree on those share it
+                    auto it = std::find_if(tabs.begin(), tabs.end(), [&](const StageTab& t) {
+                        if (!njobs) return t.d == l.d;
+                        const LaunchDesc& T = plan[t.launch].desc;
+                        return t.R == D.R && !std::memcmp(T.U, D.U, sizeof D.U);
+                    });
                     if (it == tabs.end()) {
                         const size_t at = g.desc_at + k * sizeof(LaunchDesc);
-                        it = tabs.insert(it, StageTab{l.d, (uint32_t)tab_words, D.R, at});
+                        it = tabs.insert(it, StageTab{l.d, (uint32_t)tab_words, D.R, at, g.idx[k]});
                         tab_words += 64ull * D.R;
                     }
                     D.tab_off = it->off;
@@ -133,8 +302,29 @@ struct Stage {
             bytes += g.ptab_bytes;
             align();
         }
+        upload_bytes = bytes;
+        if (!njobs) return;
+        thresh_at = bytes;
+        bytes += 8 * njobs;
+        align();
+        list_at = bytes;
+        upload_bytes = list_at + kBatchListHead;
+        for (const StageGroup& g : groups) {
+            const uint64_t grid = Stage::grid(g, kBatchMaxGrid);
+            uint64_t span = 0;
+            for (size_t k = 0; k < g.idx.size(); k++) {
+                span += row_iterations(plan[g.idx[k]].desc);
+                if (k + 1 == g.idx.size() || plan[g.idx[k + 1]].desc.job != plan[g.idx[k]].desc.job) {
+                    list_cap += batch_job_entries(span, gmin, grid);
+                    span = 0;
+                }
+            }
+        }
+        bytes = list_at + kBatchListHead + sizeof(BatchEntry) * list_cap;
+        align();
     }
 
+   public:
     // Writes the buffer's host-built bytes: zeroed counter blocks, and per group its prefix
     // offsets and descriptors.  The p-table room is the device's to fill.
     void fill(uint8_t* meta) const {
@@ -149,6 +339,11 @@ struct Stage {
                 acc += row_iterations(plan[g.idx[k]].desc);
             }
             offs[g.idx.size()] = acc;
+        }
+        if (njobs) {
+            std::memset(meta + thresh_at, 0xFF, 8 * njobs);
+            const uint32_t head[4] = {0u, (uint32_t)list_cap, 0u, 0u};  // appended, capacity
+            std::memcpy(meta + list_at, head, kBatchListHead);
         }
     }
 

@@ -36,6 +36,8 @@ GPUHASH_ETOOLONG = -4
 GPUHASH_ENOMEM = -5
 GPUHASH_MAX_MSG = 1 << 20
 GPUHASH_COLLECT_MAX = 1 << 20
+GPUHASH_BATCH_MAX_JOBS = 1 << 16
+GPUHASH_BATCH_MAX_SPAN = 1 << 38
 LAYOUT_AUTO, LAYOUT_UNIFORM, LAYOUT_CLASSIC, LAYOUT_LANETABLE = 0, 1, 2, 3
 # OR-able flags: tail-digit launches always / never (include/gpuhash.h)
 LAYOUT_TAIL_ALWAYS, LAYOUT_TAIL_NEVER = 16, 32
@@ -48,6 +50,7 @@ EXPORTED = [
     "gpuhash_set_layout_policy", "gpuhash_min", "gpuhash_min_ex",
     "gpuhash_first_below", "gpuhash_first_below_ex",
     "gpuhash_collect_below", "gpuhash_collect_below_ex",
+    "gpuhash_min_batch", "gpuhash_min_batch_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
@@ -159,6 +162,12 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
     lib.gpuhash_collect_below_ex.argtypes = [vp, u8p, sz, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(u64),
                                              ctypes.POINTER(u64), sz, ctypes.POINTER(u64)]
     lib.gpuhash_collect_below_ex.restype = ctypes.c_int
+    lib.gpuhash_min_batch.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                      ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.gpuhash_min_batch.restype = ctypes.c_int
+    lib.gpuhash_min_batch_ex.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                         ctypes.c_uint32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.gpuhash_min_batch_ex.restype = ctypes.c_int
     lib.gpuhash_hash_range.argtypes = [vp, u8p, sz, u64, u64, vp]
     lib.gpuhash_hash_range.restype = ctypes.c_int
     lib.gpuhash_hash_cpu.argtypes = [u8p, sz, u64]
@@ -256,6 +265,44 @@ class Engine:
         if rc != GPUHASH_OK:
             raise GpuHashError(rc, "gpuhash_min")
         return int(h.value), int(n.value)
+
+    def min_batch(self, jobs, rchunk: int = 0) -> list[tuple[int, int]]:
+        """[(hash, nonce)] of many independent searches in one call: entry k is what
+        min(*jobs[k]) returns, for jobs given as (msg, lower, upper) (gpuhash_min_batch_ex; one
+        scan launch per kernel variant among all the jobs, not per job).  Checked before calling
+        in: at least one and at most GPUHASH_BATCH_MAX_JOBS jobs, bounds as for min(), lower <=
+        upper, at most GPUHASH_BATCH_MAX_SPAN nonces and GPUHASH_MAX_MSG message bytes per job
+        (ValueError)."""
+        jobs = [tuple(j) for j in jobs]
+        if not 1 <= len(jobs) <= GPUHASH_BATCH_MAX_JOBS:
+            raise ValueError(f"{len(jobs)} jobs outside [1, GPUHASH_BATCH_MAX_JOBS]")
+        if isinstance(rchunk, bool) or not isinstance(rchunk, int) or not 0 <= rchunk < 1 << 32:
+            raise ValueError(f"rchunk={rchunk!r} outside [0, 2^32)")
+        msgs = []
+        for k, j in enumerate(jobs):
+            if len(j) != 3:
+                raise ValueError(f"job {k} is not (msg, lower, upper)")
+            m, lo, hi = _bytes(j[0]), _check_u64(f"jobs[{k}].lower", j[1]), _check_u64(f"jobs[{k}].upper", j[2])
+            if lo > hi:
+                raise ValueError(f"jobs[{k}]: lower={lo} > upper={hi}")
+            if hi - lo >= GPUHASH_BATCH_MAX_SPAN:
+                raise ValueError(f"jobs[{k}] spans more than GPUHASH_BATCH_MAX_SPAN nonces")
+            if len(m) > GPUHASH_MAX_MSG:
+                raise ValueError(f"jobs[{k}]: message longer than GPUHASH_MAX_MSG")
+            msgs.append(m)
+        n = len(jobs)
+        off = (ctypes.c_size_t * (n + 1))()
+        for k, m in enumerate(msgs):
+            off[k + 1] = off[k] + len(m)
+        data = ctypes.create_string_buffer(b"".join(msgs), off[n] + 1)
+        lower = (ctypes.c_uint64 * n)(*[j[1] for j in jobs])
+        upper = (ctypes.c_uint64 * n)(*[j[2] for j in jobs])
+        hashes, nonces = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        rc = self._lib.gpuhash_min_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper, rchunk,
+                                            hashes, nonces)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_min_batch")
+        return list(zip(hashes, nonces))
 
     def first_below(self, msg, lower: int, upper: int, target: int, rchunk: int = 0) -> tuple[int, int] | None:
         """(hash, nonce) of the LOWEST nonce n of the inclusive [lower, upper] with

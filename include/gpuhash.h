@@ -89,6 +89,8 @@ typedef struct gpuhash_launch_record {
                       /*    kernel was launched on (hipStreamGetDevice): evidence   */
                       /*    that the shard ran on `device`, not on device 0         */
     uint64_t lo, hi;  /* the shard's inclusive nonce range in this slice            */
+                      /*    (gpuhash_min_batch: the index of the first and the last */
+                      /*    job of the entry's run, see there)                      */
     uint64_t nonces;  /* nonces covered by the launch                               */
     double ms;        /* HIP-event time of the launch on the device's stream        */
     double sclk_mhz;  /* shader clock over the launch, measured in the kernel:      */
@@ -239,6 +241,46 @@ int gpuhash_collect_below(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, 
 int gpuhash_collect_below_ex(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
                              uint64_t upper, uint64_t target, uint32_t rchunk, uint64_t *out_nonces,
                              uint64_t *out_hashes, size_t cap, uint64_t *out_total);
+
+/* njobs independent gpuhash_min searches in one call: (out_hashes[k], out_nonces[k]) is exactly
+ * what gpuhash_min(ctx, msg_k, len_k, lower[k], upper[k]) returns -- the least hash, and the
+ * lowest nonce among equal hashes -- under every layout policy, tail flag and rchunk, however
+ * many context entries ran and in whatever order the jobs are listed.  For hosts whose searches
+ * are many and small (a server's jobs, config-1-sized requests): a gpuhash_min call costs ~70 us
+ * whatever its range, a batch runs ONE scan launch per kernel variant among all its jobs
+ * (DESIGN.md 3.11), not one per variant per job.
+ * The arrays are flat (no pointers inside structs: cgo's pointer rules).  Job k's message is
+ * msgs[msg_off[k] .. msg_off[k+1]); msg_off has njobs + 1 entries and never decreases.  Messages
+ * may be empty (msgs may be null when all are), and jobs may share or repeat a message.  The jobs
+ * are independent: overlapping ranges of one message are two separate searches.
+ * Whole-call argument errors, detected before any use of ctx's contents and before anything is
+ * written to the outputs, deterministic as gpuhash_min's: GPUHASH_EINVAL for a null pointer,
+ * njobs == 0 or njobs > GPUHASH_BATCH_MAX_JOBS, a msg_off that decreases, any lower[k] >
+ * upper[k], any job of more than GPUHASH_BATCH_MAX_SPAN nonces (one slice: split longer searches
+ * or use gpuhash_min); GPUHASH_ETOOLONG for any message over GPUHASH_MAX_MSG.
+ * A batch runs as consecutive SUB-BATCHES of whole jobs, each holding as many jobs as keep its
+ * launch metadata, result list and K+W tables within GPUHASH_BATCH_BYTES_DEFAULT bytes per
+ * context entry (env GPUHASH_BATCH_BYTES=<bytes> overrides it, up to 1 GiB; a single job always
+ * fits).  A sub-batch's jobs are cut into contiguous runs of about equal estimated cost, one per
+ * context entry, which run concurrently; a job is never split across entries.  Splitting never
+ * changes a result.
+ * Afterwards gpuhash_last_stats().nonces is the sum of the jobs' spans (saturating) and
+ * .launches the scan launches that ran; gpuhash_last_launches gives one record per kernel
+ * variant per context entry per sub-batch, with `nonces` the total of that variant's launches
+ * and -- for batch records only -- `lo` and `hi` the INDEX of the first and the last job of that
+ * entry's run, not nonces.  Threading, device-guard behaviour, errors and the no-exception rule
+ * are as for gpuhash_min.  Replaces nothing in the reference (its miner takes one job at a time). */
+#define GPUHASH_BATCH_MAX_JOBS (1u << 16)
+#define GPUHASH_BATCH_MAX_SPAN (1ull << 38)   /* nonces per job: one slice */
+#define GPUHASH_BATCH_BYTES_DEFAULT (32u << 20)
+int gpuhash_min_batch(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                      const uint64_t *lower, const uint64_t *upper,
+                      uint64_t *out_hashes, uint64_t *out_nonces);
+
+/* Same batch, caller-chosen work-item granularity (as gpuhash_min_ex). */
+int gpuhash_min_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                         const uint64_t *lower, const uint64_t *upper, uint32_t rchunk,
+                         uint64_t *out_hashes, uint64_t *out_nonces);
 
 /* out[i] = Hash(msg, lower + i) for i < count, computed on the first device by the
  * SAME kernels as gpuhash_min (per-nonce dump mode).  count <= 2^26; lower + count - 1

@@ -141,5 +141,46 @@ func (e *Engine) CollectBelow(data string, lower, upper, target uint64, max int)
 	return uint64(t), nonces[:k], hashes[:k], nil
 }
 
+// Job is one search of a batch: the inclusive [Lower, Upper] of Data.
+type Job struct {
+	Data         string
+	Lower, Upper uint64
+}
+
+// MinBatch answers many independent searches in one call: hashes[k], nonces[k] are exactly
+// what Min(jobs[k].Data, jobs[k].Lower, jobs[k].Upper) returns.  For many small jobs (a
+// server's chunks, config-1-sized requests): the engine runs one kernel launch per kernel
+// variant among all the jobs, where a loop of Min calls pays ~70 us per call.  At most
+// GPUHASH_BATCH_MAX_JOBS jobs of at most GPUHASH_BATCH_MAX_SPAN nonces each.
+// The ABI takes flat arrays (no Go pointer inside memory passed to C): the messages end to
+// end, their offsets, and the bounds.
+func (e *Engine) MinBatch(jobs []Job) (hashes, nonces []uint64, err error) {
+	n := len(jobs)
+	if n == 0 || n > int(C.GPUHASH_BATCH_MAX_JOBS) {
+		return nil, nil, rcErr(C.GPUHASH_EINVAL)
+	}
+	off := make([]C.size_t, n+1)
+	lower := make([]C.uint64_t, n)
+	upper := make([]C.uint64_t, n)
+	msgs := make([]byte, 0, 64*n)
+	for k, j := range jobs {
+		msgs = append(msgs, j.Data...)
+		off[k+1] = C.size_t(len(msgs))
+		lower[k] = C.uint64_t(j.Lower)
+		upper[k] = C.uint64_t(j.Upper)
+	}
+	var p *C.uint8_t
+	if len(msgs) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&msgs[0]))
+	}
+	hashes = make([]uint64, n)
+	nonces = make([]uint64, n)
+	rc := C.gpuhash_min_batch(e.ctx, p, &off[0], C.size_t(n), &lower[0], &upper[0], (*C.uint64_t)(unsafe.Pointer(&hashes[0])), (*C.uint64_t)(unsafe.Pointer(&nonces[0])))
+	if err = rcErr(rc); err != nil {
+		return nil, nil, err
+	}
+	return hashes, nonces, nil
+}
+
 // Close releases the devices.
 func (e *Engine) Close() { C.gpuhash_close(e.ctx) }
