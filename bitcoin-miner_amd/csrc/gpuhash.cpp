@@ -71,6 +71,7 @@ struct Dev {
     // of the run
     std::vector<BatchEntry> bat_list;
     std::vector<uint64_t> bat_h, bat_n;
+    std::vector<uint8_t> bat_found;  // first-hit batch: the job has an entry
     bool used = false;
     double kernel_ms = 0;
     uint32_t launches = 0;
@@ -259,6 +260,11 @@ struct ModeWiring {
     // entries are copied and folded per job by the (hash, nonce) key.  d_thresh, d_cands, d_ncand
     // and d_best are not used.
     bool batch;
+    // A batch whose per-job words are pairs, {the lowest qualifying nonce found so far, the job's
+    // target}, in a stage whose launches ascend in digits (stage.h, Stage::by_digits).  The list
+    // holds real hits only and is folded per job by the LOWEST NONCE; a job without an entry has
+    // no hit.
+    bool batch_first;
 };
 constexpr ModeWiring kWiring[] = {
     /* kScanMin     */ {false, false, false, true},
@@ -266,6 +272,7 @@ constexpr ModeWiring kWiring[] = {
     /* kScanFirst   */ {false, true, true, true},
     /* kScanCollect */ {true, true, false, false},
     /* kScanBatch   */ {false, false, false, false, true},
+    /* kScanFirstBatch */ {false, false, false, false, true, true},
 };
 
 // dev_run, phase 1: reserves the entry's buffers, writes and uploads the launch metadata in one
@@ -398,10 +405,18 @@ static int decode(Dev& d, const ScanJob& job, const Stage& st) {
         }
         d.bat_h.assign(st.njobs, ~0ull);
         d.bat_n.assign(st.njobs, ~0ull);
+        d.bat_found.assign(st.njobs, 0);
+        const bool first = kWiring[job.mode].batch_first;
         for (const BatchEntry& e : d.bat_list) {
             if (e.job >= st.njobs) return GPUHASH_EHIP;
             uint64_t &h = d.bat_h[e.job], &x = d.bat_n[e.job];
-            if (e.hash < h || (e.hash == h && e.nonce < x)) { h = e.hash; x = e.nonce; }
+            if (first) {  // the lowest nonce; 2^64-1 is a legal one, so the flag says "any"
+                if (!d.bat_found[e.job] || e.nonce < x) { h = e.hash; x = e.nonce; }
+                d.bat_found[e.job] = 1;
+            } else if (e.hash < h || (e.hash == h && e.nonce < x)) {
+                h = e.hash;
+                x = e.nonce;
+            }
         }
         return GPUHASH_OK;
     }
@@ -441,15 +456,16 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
 
 // Runs one entry's run of a sub-batch: the jobs [first, end) of `jobs`, whose plans are moved
 // into the stage; index0 is the batch index of jobs[0], for the launch records.
+// target: null for gpuhash_min_batch, else the targets of jobs[0..) for gpuhash_first_below_batch.
 static int dev_run_batch(Dev& d, std::vector<PlannedJob>& jobs, size_t first, size_t end, size_t index0,
-                         uint32_t rchunk) {
+                         uint32_t rchunk, const uint64_t* target = nullptr) {
     d.used = true;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(d.ord));
     std::vector<std::vector<Launch>> plans(end - first);
     for (size_t k = first; k < end; k++) plans[k - first] = std::move(jobs[k].plan);
-    const Stage st(plans, rchunk);
-    const ScanJob job{kScanBatch};
+    const Stage st = target ? Stage(plans, target + first, rchunk) : Stage(plans, rchunk);
+    const ScanJob job{target ? kScanFirstBatch : kScanBatch};
     std::vector<unsigned int> grids;
     int rc = stage_upload(d, st, job, grids);
     if (!rc) rc = arm_and_launch(d, st, job, 0, grids);
@@ -802,6 +818,83 @@ int gpuhash_min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_o
     return gpuhash_min_batch_ex(ctx, msgs, msg_off, njobs, lower, upper, 0, out_hashes, out_nonces);
 }
 
+// gpuhash_first_below_batch_ex, its arguments checked: min_batch's sub-batches and runs, each run
+// one first-hit batch stage (stage.h, Stage::by_digits) and one launch per group of it.
+static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                             const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                             uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Call call(ctx);
+    std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
+    std::vector<uint8_t> rf(njobs);
+    const int policy = ctx->policy;
+    auto plan = [&](size_t k) {
+        const size_t len = msg_off[k + 1] - msg_off[k];
+        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy,
+                        /*host_ptab=*/false, /*pair=*/true);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
+        const std::vector<std::pair<size_t, size_t>> runs = batch_runs(jobs, ctx->devs.size());
+        const int rc = call.run_each(runs.size(), [&](size_t r) {
+            Dev& d = ctx->devs[r];
+            d.rc = guarded([&] {
+                return dev_run_batch(d, jobs, runs[r].first, runs[r].second, first, rchunk, target + first);
+            });
+        });
+        if (rc) return rc;
+        for (size_t r = 0; r < runs.size(); r++) {
+            const Dev& d = ctx->devs[r];
+            for (size_t k = runs[r].first; k < runs[r].second; k++) {
+                rh[first + k] = d.bat_h[k - runs[r].first];
+                rn[first + k] = d.bat_n[k - runs[r].first];
+                rf[first + k] = d.bat_found[k - runs[r].first];
+            }
+        }
+        return GPUHASH_OK;
+    };
+    if (int rc = for_each_sub_batch(njobs, batch_bytes_bound(), plan, run)) return rc;
+    uint64_t nonces = 0;  // what an ascending scan of every job would have examined
+    for (size_t k = 0; k < njobs; k++) {
+        const uint64_t n = (rf[k] ? rn[k] : upper[k]) - lower[k] + 1;  // <= GPUHASH_BATCH_MAX_SPAN
+        nonces = nonces + n < nonces ? ~0ull : nonces + n;
+    }
+    call.finish_nonces(nonces);
+    for (size_t k = 0; k < njobs; k++) {
+        out_found[k] = rf[k] ? 1 : 0;
+        if (!rf[k]) continue;  // its outputs stay untouched
+        out_hashes[k] = rh[k];
+        out_nonces[k] = rn[k];
+    }
+    return GPUHASH_OK;
+}
+
+int gpuhash_first_below_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                 const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                 uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+    if (!ctx || !msg_off || !lower || !upper || !target || !out_hashes || !out_nonces || !out_found)
+        return GPUHASH_EINVAL;
+    if (njobs == 0 || njobs > GPUHASH_BATCH_MAX_JOBS) return GPUHASH_EINVAL;
+    bool too_long = false;
+    for (size_t k = 0; k < njobs; k++) {
+        if (msg_off[k + 1] < msg_off[k] || lower[k] > upper[k]) return GPUHASH_EINVAL;
+        if (upper[k] - lower[k] >= GPUHASH_BATCH_MAX_SPAN) return GPUHASH_EINVAL;
+        too_long = too_long || msg_off[k + 1] - msg_off[k] > GPUHASH_MAX_MSG;
+    }
+    if (!msgs && msg_off[njobs] != msg_off[0]) return GPUHASH_EINVAL;
+    if (too_long) return GPUHASH_ETOOLONG;
+    return guarded([&] {
+        return first_below_batch(ctx, msgs, msg_off, njobs, lower, upper, target, rchunk, out_hashes, out_nonces,
+                                 out_found);
+    });
+}
+
+int gpuhash_first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                              const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                              uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+    return gpuhash_first_below_batch_ex(ctx, msgs, msg_off, njobs, lower, upper, target, 0, out_hashes, out_nonces,
+                                        out_found);
+}
+
 int gpuhash_min(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
                 uint64_t upper, uint64_t* out_hash, uint64_t* out_nonce) {
     return gpuhash_min_ex(ctx, msg, msg_len, lower, upper, 0, out_hash, out_nonce);
@@ -871,9 +964,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.6 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.7 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.6 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.7 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

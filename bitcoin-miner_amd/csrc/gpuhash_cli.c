@@ -18,6 +18,9 @@
  *                                         without blanks; empty lines are skipped); prints one
  *                                         "Result <hash> <nonce>" per job, in order, from ONE
  *                                         gpuhash_min_batch call ("-" reads standard input)
+ *   gpuhash_cli --batch-below FILE     -> lines "MSG LOWER UPPER TARGET"; prints per job, in order,
+ *                                         "Result <hash> <nonce>" of the lowest nonce whose hash is
+ *                                         <= TARGET, or "None", from ONE gpuhash_first_below_batch call
  *   gpuhash_cli --version
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
  */
@@ -43,8 +46,9 @@ static int fail(const char *what, int rc) {
     return 3;
 }
 
-/* --batch: every job of the file in one gpuhash_min_batch call. */
-static int batch_main(const char *path) {
+/* --batch: every job of the file in one gpuhash_min_batch call; --batch-below (below != 0): in
+ * one gpuhash_first_below_batch call, each line with a TARGET. */
+static int batch_main(const char *path, int below) {
     FILE *f = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
     if (!f) {
         fprintf(stderr, "cannot open %s\n", path);
@@ -53,7 +57,7 @@ static int batch_main(const char *path) {
     size_t njobs = 0, cap = 0, bytes = 0, bytes_cap = 0;
     uint8_t *msgs = NULL;
     size_t *off = NULL;
-    uint64_t *lower = NULL, *upper = NULL;
+    uint64_t *lower = NULL, *upper = NULL, *target = NULL;
     char *line = NULL;
     size_t line_cap = 0;
     int status = 0;
@@ -62,9 +66,11 @@ static int batch_main(const char *path) {
         const char *m = strtok_r(line, " \t\r\n", &save);
         if (!m) continue; /* an empty line */
         const char *lo = strtok_r(NULL, " \t\r\n", &save), *hi = strtok_r(NULL, " \t\r\n", &save);
-        uint64_t a, b;
-        if (!lo || !hi || strtok_r(NULL, " \t\r\n", &save) || parse_u64(lo, &a) || parse_u64(hi, &b)) {
-            fprintf(stderr, "line %zu: expected MSG LOWER UPPER\n", njobs + 1);
+        const char *tg = below ? strtok_r(NULL, " \t\r\n", &save) : NULL;
+        uint64_t a, b, t = 0;
+        if (!lo || !hi || (below && (!tg || parse_u64(tg, &t))) || strtok_r(NULL, " \t\r\n", &save) ||
+            parse_u64(lo, &a) || parse_u64(hi, &b)) {
+            fprintf(stderr, "line %zu: expected MSG LOWER UPPER%s\n", njobs + 1, below ? " TARGET" : "");
             status = 2;
             break;
         }
@@ -74,12 +80,13 @@ static int batch_main(const char *path) {
             off = (size_t *)realloc(off, (cap + 1) * sizeof *off);
             lower = (uint64_t *)realloc(lower, cap * sizeof *lower);
             upper = (uint64_t *)realloc(upper, cap * sizeof *upper);
+            target = (uint64_t *)realloc(target, cap * sizeof *target);
         }
         if (bytes + len + 1 > bytes_cap) {
             bytes_cap = 2 * (bytes + len + 1);
             msgs = (uint8_t *)realloc(msgs, bytes_cap);
         }
-        if (!off || !lower || !upper || !msgs) {
+        if (!off || !lower || !upper || !target || !msgs) {
             fprintf(stderr, "out of memory\n");
             status = 3;
             break;
@@ -89,11 +96,13 @@ static int batch_main(const char *path) {
         bytes += len;
         lower[njobs] = a;
         upper[njobs] = b;
+        target[njobs] = t;
         off[++njobs] = bytes;
     }
     free(line);
     if (f != stdin) fclose(f);
     uint64_t *h = NULL, *n = NULL;
+    int *found = NULL;
     if (!status && njobs == 0) {
         fprintf(stderr, "no jobs in %s\n", path);
         status = 2;
@@ -101,10 +110,27 @@ static int batch_main(const char *path) {
     if (!status) {
         h = (uint64_t *)malloc(njobs * sizeof *h);
         n = (uint64_t *)malloc(njobs * sizeof *n);
+        found = (int *)malloc(njobs * sizeof *found);
         gpuhash_ctx *ctx = NULL;
-        int rc = h && n ? gpuhash_open(NULL, 0, &ctx) : GPUHASH_ENOMEM;
+        int rc = h && n && found ? gpuhash_open(NULL, 0, &ctx) : GPUHASH_ENOMEM;
         if (rc) {
             status = fail("gpuhash_open", rc);
+        } else if (below) {
+            rc = gpuhash_first_below_batch(ctx, msgs, off, njobs, lower, upper, target, h, n, found);
+            if (rc) status = fail("gpuhash_first_below_batch", rc);
+            for (size_t k = 0; k < njobs && !status; k++) { /* --below's self-check, per found job */
+                if (found[k] && (gpuhash_hash_cpu(msgs + off[k], off[k + 1] - off[k], n[k]) != h[k] || h[k] > target[k] ||
+                                 n[k] < lower[k] || n[k] > upper[k])) {
+                    fprintf(stderr, "self-check failed at job %zu: Hash(msg, %" PRIu64 ") != %" PRIu64
+                                    " or above the target\n", k, n[k], h[k]);
+                    status = 4;
+                }
+            }
+            for (size_t k = 0; k < njobs && !status; k++) {
+                if (found[k]) printf("Result %" PRIu64 " %" PRIu64 "\n", h[k], n[k]);
+                else printf("None\n");
+            }
+            gpuhash_close(ctx);
         } else {
             rc = gpuhash_min_batch(ctx, msgs, off, njobs, lower, upper, h, n);
             if (rc) status = fail("gpuhash_min_batch", rc);
@@ -121,6 +147,8 @@ static int batch_main(const char *path) {
     }
     free(h);
     free(n);
+    free(found);
+    free(target);
     free(msgs);
     free(off);
     free(lower);
@@ -133,13 +161,14 @@ int main(int argc, char **argv) {
         printf("%s\n", gpuhash_version());
         return 0;
     }
-    if (argc == 3 && strcmp(argv[1], "--batch") == 0) return batch_main(argv[2]);
+    if (argc == 3 && strcmp(argv[1], "--batch") == 0) return batch_main(argv[2], 0);
+    if (argc == 3 && strcmp(argv[1], "--batch-below") == 0) return batch_main(argv[2], 1);
     const int range_mode = argc == 5 && strcmp(argv[1], "--range") == 0;
     const int below_mode = argc == 6 && strcmp(argv[1], "--below") == 0;
     const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
     if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --batch-below FILE | --version\n", argv[0]);
         return 2;
     }
     const int opt = range_mode || below_mode || all_mode;

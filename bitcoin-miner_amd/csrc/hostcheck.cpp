@@ -233,6 +233,12 @@ struct Staged {
         read_groups();
     }
 
+    // A first-hit batch stage: as above, with target[k] job k's target.
+    Staged(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk)
+        : st(plans, target, rchunk), meta(st.bytes) {
+        read_groups();
+    }
+
    private:
     void read_groups() {
         st.fill(meta.data());
@@ -704,6 +710,276 @@ int hostcheck_stage_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t
     }
     *bytes = st.bytes;
     const uint64_t ex[8] = {st.upload_bytes, st.thresh_at, 8 * st.njobs, st.list_at, st.list_cap,
+                            sizeof(BatchEntry), st.tabs.size(), st.tab_words};
+    std::memcpy(extra, ex, sizeof ex);
+    if (meta && meta_cap >= st.bytes) {
+        std::memset(meta, 0, st.bytes);
+        st.fill(meta);
+    }
+    return (int)st.groups.size();
+}
+
+}  // extern "C"
+
+// ---- first-hit batch (gpuhash_first_below_batch): CPU replay of the kernel's MODE 5 ----
+//
+// A first-hit batch stage's groups in stage order (ascending digits), pieces, parts and masks as
+// k_scan<.., 5> walks them, from the bytes fill() wrote: MODE 4's descriptor lookup and job change,
+// MODE 2's slow path, skip rule and drain against the current job's words.  A workgroup is replayed
+// with its four waves' hits; its pieces ascend.  What a GPU decides by timing is chosen by a seed:
+// which workgroup takes which piece, and -- under a shuffle -- what a workgroup reads in a bound
+// word: now and then not the word as it stands but as it stood when the group's launch began, the
+// stalest value a read in that launch can return (the launches run back to back on one stream, so
+// whatever earlier launches published is there).
+// The drain (atomicMax on the work counter) is replayed as in hostcheck_first_below: as cancelled
+// position ranges that drop those positions from every piece visited later, in whatever order,
+// which skips more than the kernel can.
+
+namespace {
+
+struct FirstWg {
+    std::vector<size_t> pieces;  // ascending
+    size_t next = 0;
+    uint64_t n[4] = {0, 0, 0, 0}, h[4] = {0, 0, 0, 0};
+    bool found[4] = {false, false, false, false};
+    uint32_t job = 0xFFFFFFFFu;  // kNoJob
+    uint64_t bound = ~0ull;      // as read at the last grab or job change
+    int idx = 0;                 // batch_find's hint
+};
+
+// What the replay did for one job.
+struct JobTrace {
+    uint64_t lo = 0, hashed = 0, largest = 0;
+    std::vector<bool> seen;  // per nonce of the job's range, while it is small enough to hold
+    bool twice = false;      // some nonce was hashed twice: the pieces overlapped
+};
+
+struct FirstBatchReplay {
+    const Staged& run;
+    std::vector<uint64_t> words;  // {bound, target} per job, as fill() armed them
+    std::vector<uint64_t> at_launch;  // the bounds when the current group's launch began
+    std::vector<BatchEntry> list;
+    std::vector<JobTrace>& trace;
+    std::vector<std::pair<uint64_t, uint64_t>> cancelled;  // of the current group, [from, to)
+    Rng* jitter = nullptr;
+
+    FirstBatchReplay(const Staged& r, std::vector<JobTrace>& t) : run(r), words(2 * r.st.njobs), trace(t) {
+        std::memcpy(words.data(), r.meta.data() + r.st.thresh_at, 16 * r.st.njobs);
+    }
+
+    uint64_t read_bound(uint32_t job) {
+        if (jitter && jitter->next() % 4 == 0) return at_launch[job];
+        return words[2 * (size_t)job];
+    }
+
+    void flush(FirstWg& wg) {
+        if (wg.job == 0xFFFFFFFFu) return;
+        bool any = false;
+        uint64_t bn = 0, bh = 0;
+        for (int i = 0; i < 4; i++)
+            if (wg.found[i] && (!any || wg.n[i] < bn)) { bn = wg.n[i]; bh = wg.h[i]; any = true; }
+        if (any) list.push_back(BatchEntry{bh, bn, wg.job, 0});
+    }
+
+    bool is_cancelled(uint64_t pos, uint64_t& to) const {
+        for (const auto& c : cancelled)
+            if (pos >= c.first && pos < c.second) { to = c.second; return true; }
+        return false;
+    }
+
+    void piece(const VGroup& g, FirstWg& wg, uint64_t x, uint64_t end) {
+        if (wg.job != 0xFFFFFFFFu) wg.bound = read_bound(wg.job);  // the grab
+        while (x < end) {
+            uint64_t to;
+            if (is_cancelled(x, to)) {  // never handed out
+                x = std::min(to, end);
+                continue;
+            }
+            if (jitter && jitter->next() % 4 == 0) wg.idx = (int)(jitter->next() % g.ls.size());
+            const int i = wg.idx = BatchReplay::find(g, wg.idx, x);
+            const LaunchDesc& D = g.descs[i];
+            const Launch& l = *g.ls[(size_t)i];
+            const uint32_t rel = (uint32_t)(x - g.offs[i]);
+            const uint32_t row = rel / D.R, r0 = rel - row * D.R;
+            const uint64_t left = end - x;
+            const uint32_t r1 = (uint64_t)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
+            if (D.job != wg.job) {
+                flush(wg);
+                wg.job = D.job;
+                for (bool& f : wg.found) f = false;
+                wg.bound = read_bound(D.job);
+            }
+            const uint64_t target = words[2 * (size_t)D.job + 1];
+            const uint64_t lb = std::max(part_min_nonce(D, l.C2, row, r0), desc_min_nonce(D, l.C2));
+            if (lb > wg.bound) {
+                if (l.C2 != 3) {
+                    // the drain, with the kernel's look at the next 64 descriptors: the unbroken
+                    // run of those that lie wholly above their own job's bound goes with it
+                    int k = i + 1;
+                    while (k < (int)g.ls.size() && k <= i + 64 &&
+                           desc_min_nonce(g.descs[k], l.C2) > read_bound(g.descs[k].job))
+                        k++;
+                    cancelled.push_back({x, g.offs[k]});
+                    x = std::min<uint64_t>(g.offs[i + 1], end);
+                } else {
+                    x += r1 - r0;
+                }
+                continue;
+            }
+            const Part pt{&l, &D, row, r0, r1, x, g.offs[i + 1]};
+            JobTrace& tr = trace[D.job];
+            for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                tr.hashed++;
+                tr.largest = std::max(tr.largest, n);
+                if (n - tr.lo < tr.seen.size()) {
+                    tr.twice = tr.twice || tr.seen[n - tr.lo];
+                    tr.seen[n - tr.lo] = true;
+                }
+                const uint64_t h = replay_hash(l, p, r);
+                if (h > target) return;
+                const int w = (int)(((p - D.p_first) & 255u) >> 6);
+                if (wg.found[w] && n >= wg.n[w]) return;
+                wg.n[w] = n;
+                wg.h[w] = h;
+                wg.found[w] = true;
+                words[2 * (size_t)D.job] = std::min(words[2 * (size_t)D.job], n);  // atomicMin, at the hit
+            });
+            x += r1 - r0;
+        }
+    }
+
+    // BatchReplay::group's workgroups and orders.
+    void group(size_t gi, uint64_t order_seed, Rng& rng) {
+        const VGroup& g = run.groups[gi];
+        const size_t np = g.pieces.size();
+        jitter = order_seed > 1 ? &rng : nullptr;
+        cancelled.clear();
+        at_launch.resize(run.st.njobs);
+        for (size_t k = 0; k < run.st.njobs; k++) at_launch[k] = words[2 * k];
+        const size_t grid = Stage::grid(run.st.groups[gi], std::min<unsigned int>(kReplayGrid, kBatchMaxGrid));
+        const size_t W = order_seed == 0 ? 1 : order_seed == 1 ? std::min(grid, np)
+                                                               : std::min({grid, np, (size_t)(2 + rng.next() % 7)});
+        std::vector<FirstWg> wgs(W);
+        for (size_t k = 0; k < np; k++) {
+            const size_t w = order_seed == 0 ? 0 : order_seed == 1 ? k * W / np : rng.next() % W;
+            wgs[w].pieces.push_back(k);
+        }
+        auto step = [&](FirstWg& wg) {
+            const auto& pc = g.pieces[wg.pieces[wg.next++]];
+            piece(g, wg, pc.first, pc.second);
+            if (wg.next == wg.pieces.size()) flush(wg);  // the end of the kernel
+        };
+        if (order_seed <= 1) {
+            for (size_t w = W; w-- > 0;)
+                while (wgs[w].next < wgs[w].pieces.size()) step(wgs[w]);
+            return;
+        }
+        std::vector<size_t> live;
+        for (size_t w = 0; w < W; w++)
+            if (!wgs[w].pieces.empty()) live.push_back(w);
+        while (!live.empty()) {
+            const size_t at = rng.next() % live.size();
+            FirstWg& wg = wgs[live[at]];
+            step(wg);
+            if (wg.next == wg.pieces.size()) live.erase(live.begin() + (long)at);
+        }
+    }
+};
+
+constexpr uint64_t kTraceMaxSpan = 1ull << 24;  // a job's per-nonce record is kept up to this span
+
+}  // namespace
+
+extern "C" {
+
+// gpuhash_first_below_batch as the engine runs it: hostcheck_min_batch's sub-batches and runs, each
+// run a first-hit batch stage replayed group by group in stage order, with the order of a group's
+// pieces chosen by order_seed (0, 1 or a shuffle, see FirstBatchReplay).  Returns 0, or -2 if some
+// nonce was hashed twice, and per job out_found, and (out_hashes, out_nonces) when found (untouched
+// otherwise), and in out_trace[3k..3k+2] what the replay hashed for job k: how many nonces, the
+// largest of them (0 when none), and how many of the nonces from lower[k] to the answer it hashed
+// (found jobs of at most 2^24 nonces; else all ones).  out_fill is hostcheck_min_batch's.
+int hostcheck_first_below_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs, const uint64_t* lower,
+                                const uint64_t* upper, const uint64_t* target, uint32_t rchunk, int policy,
+                                uint64_t order_seed, uint64_t batch_bytes, int nshards, uint64_t* out_hashes,
+                                uint64_t* out_nonces, int* out_found, uint64_t* out_trace, uint64_t* out_fill) {
+    if (!msg_off || !lower || !upper || !target || !out_hashes || !out_nonces || !out_found || !out_trace ||
+        !out_fill || !njobs || nshards < 1)
+        return -1;
+    for (uint64_t k = 0; k < njobs; k++)
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+    Rng rng{order_seed};
+    uint64_t fill[4] = {0, 0, 0, 0};
+    bool twice = false;
+    auto plan = [&](size_t k) {
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy,
+                        /*host_ptab=*/true, /*pair=*/true);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
+        fill[3]++;
+        for (const auto& r : batch_runs(jobs, (size_t)nshards)) {
+            const size_t n = r.second - r.first, at = first + r.first;
+            std::vector<std::vector<Launch>> plans(n);
+            for (size_t k = r.first; k < r.second; k++) plans[k - r.first] = std::move(jobs[k].plan);
+            const Staged staged(plans, target + at, rchunk);
+            std::vector<JobTrace> trace(n);
+            for (size_t k = 0; k < n; k++) {
+                trace[k].lo = lower[at + k];
+                const uint64_t span = upper[at + k] - lower[at + k];
+                if (span < kTraceMaxSpan) trace[k].seen.assign((size_t)span + 1, false);
+            }
+            FirstBatchReplay rep(staged, trace);
+            for (size_t gi = 0; gi < staged.groups.size(); gi++) rep.group(gi, order_seed, rng);
+            if (rep.list.size() >= fill[0]) { fill[0] = rep.list.size(); fill[1] = staged.st.list_cap; }
+            fill[2] += rep.list.size() > staged.st.list_cap ? 1 : 0;
+            for (size_t k = 0; k < n; k++) out_found[at + k] = 0;
+            for (const BatchEntry& e : rep.list) {  // the host's fold: the lowest nonce
+                const size_t k = at + e.job;
+                if (!out_found[k] || e.nonce < out_nonces[k]) { out_hashes[k] = e.hash; out_nonces[k] = e.nonce; }
+                out_found[k] = 1;
+            }
+            for (size_t k = 0; k < n; k++) {
+                const JobTrace& t = trace[k];
+                twice = twice || t.twice;
+                uint64_t upto = ~0ull;
+                if (out_found[at + k] && !t.seen.empty()) {
+                    upto = 0;
+                    for (uint64_t i = 0; i <= out_nonces[at + k] - t.lo; i++) upto += t.seen[(size_t)i] ? 1 : 0;
+                }
+                const uint64_t row[3] = {t.hashed, t.largest, upto};
+                std::memcpy(out_trace + 3 * (at + k), row, sizeof row);
+            }
+        }
+        return 0;
+    };
+    if (int rc = for_each_sub_batch((size_t)njobs, batch_bytes_bound(batch_bytes), plan, run)) return rc;
+    std::memcpy(out_fill, fill, sizeof fill);
+    return twice ? -2 : 0;
+}
+
+// The stage of ONE run of a first-hit batch, as hostcheck_stage_batch gives a batch's: the same
+// words (the per-job region's size is then 16 bytes per job), the groups in launch order.
+int hostcheck_stage_first_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs, const uint64_t* lower,
+                                const uint64_t* upper, const uint64_t* target, uint32_t rchunk, uint64_t* out,
+                                int cap, uint64_t* bytes, uint64_t* extra, uint8_t* meta, uint64_t meta_cap) {
+    if (!msg_off || !lower || !upper || !target || !bytes || !extra || !njobs) return -1;
+    std::vector<std::vector<Launch>> plans(njobs);
+    for (uint64_t k = 0; k < njobs; k++) {
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        plan_range(len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k], plans[k], rchunk, g_policy);
+    }
+    const Stage st(plans, target, rchunk);
+    for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
+        const StageGroup& g = st.groups[(size_t)i];
+        const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,
+                                  (uint64_t)g.c, g.total, g.nonces, g.work_at, g.offs_at, g.desc_at, g.ptab_at,
+                                  sizeof(LaunchDesc) * g.idx.size(), g.ptab_bytes};
+        std::memcpy(out + 14 * i, row, sizeof row);
+    }
+    *bytes = st.bytes;
+    const uint64_t ex[8] = {st.upload_bytes, st.thresh_at, st.job_words_bytes() * st.njobs, st.list_at, st.list_cap,
                             sizeof(BatchEntry), st.tabs.size(), st.tab_words};
     std::memcpy(extra, ex, sizeof ex);
     if (meta && meta_cap >= st.bytes) {

@@ -2,7 +2,8 @@
 // kernels_{plain,ut,misc}.hip, their first-hit MODE 2 instances in
 // kernels_{plain,ut,misc}_first.hip and their collecting MODE 3 instances in
 // kernels_{plain,ut,misc}_collect.hip and their batch MODE 4 instances in
-// kernels_{plain,ut,misc}_batch.hip; see scan_decl.h) and the candidate reduce.
+// kernels_{plain,ut,misc}_batch.hip and their first-hit batch MODE 5 instances in
+// kernels_{plain,ut,misc}_firstbatch.hip; see scan_decl.h) and the candidate reduce.
 #include <atomic>
 
 #include "kernels.h"
@@ -133,6 +134,7 @@ struct Occupancy {
 
 unsigned int grid_for(int J, int C2, int EX, int mode, int device) {
     if (!valid_variant(J, C2, EX)) return 0;
+    if (mode == 5) return with_variant<5>(J, C2, EX, Occupancy{device});
     if (mode == 4) return with_variant<4>(J, C2, EX, Occupancy{device});
     if (mode == 3) return with_variant<3>(J, C2, EX, Occupancy{device});
     if (mode == 2) return with_variant<2>(J, C2, EX, Occupancy{device});
@@ -142,6 +144,7 @@ unsigned int grid_for(int J, int C2, int EX, int mode, int device) {
 
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a) {
     if (!valid_variant(J, C2, EX) || a.grid == 0 || a.ndesc <= 0) return hipErrorInvalidValue;
+    if (mode == 5) return with_variant<5>(J, C2, EX, Launcher{a});
     if (mode == 4) return with_variant<4>(J, C2, EX, Launcher{a});
     if (mode == 3) return with_variant<3>(J, C2, EX, Launcher{a});
     if (mode == 2) return with_variant<2>(J, C2, EX, Launcher{a});

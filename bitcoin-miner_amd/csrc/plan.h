@@ -120,6 +120,17 @@ GPUHASH_HD inline uint64_t part_min_nonce(const LaunchDesc& D, int C2, uint32_t 
     return (D.base + p * D.R + r0) * D.stride + D.tail;
 }
 
+// The lowest nonce descriptor D holds: its first lane value at that lane's first loop value.
+// part_min_nonce starts a row's bound at loop value r0 even where r_first masks the nonces below
+// it, so the bound of the descriptor's first parts can lie below every nonce of the descriptor --
+// below its digit count, even.  The first-hit batch (gpuhash_first_below_batch: the scan kernel's
+// MODE 5 and its CPU replay) takes the larger of the two, which is a lower bound of the part's
+// nonces all the same and grows with the part's position as part_min_nonce does.
+GPUHASH_HD inline uint64_t desc_min_nonce(const LaunchDesc& D, int C2) {
+    if (C2 == 3) return D.base + D.p_first;
+    return (D.base + (uint64_t)D.p_first * D.R + D.r_first) * D.stride + D.tail;
+}
+
 struct Launch {
     int J;          // loop word index in block B
     int C2;         // 1: lane block B-1 compressed per lane; 2: and W_0, W_1 are loop words

@@ -9,7 +9,8 @@
 // The first-hit instances (MODE 2) of each family are in kernels_{plain,ut,misc}_first.hip,
 // built with that family's options, and the collecting instances (MODE 3) likewise in
 // kernels_{plain,ut,misc}_collect.hip, and the batch instances (MODE 4) in
-// kernels_{plain,ut,misc}_batch.hip.
+// kernels_{plain,ut,misc}_batch.hip, and the first-hit batch instances (MODE 5) in
+// kernels_{plain,ut,misc}_firstbatch.hip.
 // kernels.hip launches them through these declarations only, so nothing is implicitly
 // instantiated there.
 #pragma once

@@ -38,6 +38,12 @@
 // MODE 4 is MODE 0 for a batch of independent jobs, gpuhash_min_batch (BatchState, below).  Its
 // instances live in kernels_*_batch.hip, and the other modes compile to the same machine code
 // with or without it.
+//
+// MODE 5 is MODE 2 for a batch of independent jobs, gpuhash_first_below_batch: MODE 2's per-nonce
+// test, slow path, skip and drain rules against the CURRENT JOB's bound and target, and MODE 4's
+// descriptor lookup, job change and result list (first_batch_flush, below).  Its instances live in
+// kernels_*_firstbatch.hip, and the other modes compile to the same machine code with or without
+// it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -354,6 +360,75 @@ __device__ __forceinline__ void batch_flush(const WaveBest& wb, uint32_t job,
     __syncthreads();  // sh_best is free again
 }
 
+// MODE 5 (first-hit batch, gpuhash_first_below_batch): MODE 2's question for many independent jobs
+// in launches that run in ascending digit order (stage.h, Stage::by_digits).  k_scan's arguments
+// are MODE 4's, except that `thresh` holds TWO words per job: thresh[2 * job] is the job's bound,
+// the lowest qualifying nonce found so far (armed to all ones), thresh[2 * job + 1] its target.
+// The workgroup's FirstState belongs to one job at a time: `bound` and `target` are the current
+// job's, and a wave's `found`, `n`, `h` its lowest-nonce hit FOR THAT JOB.  Per nonce nothing
+// differs from MODE 2 (wb.T is the high word of the current job's target); first_hit lowers the
+// job's bound at the hit.  At a job change (MODE 4's place: between rows, all four waves meeting
+// the barriers) the workgroup appends its lowest-nonce hit for the job it leaves, if it has one,
+// and thread 0 publishes the new job's bound and target through LDS; one more flush ends the
+// kernel.  The host folds the list per job by the lowest nonce.  Exactness is MODE 2's, job by job:
+// a job's bound only ever holds a qualifying nonce of that job, so it never drops below the job's
+// answer; a part is skipped, and the rest of its descriptor (one job's) taken off the work
+// counter, only when all its nonces lie above the bound; so the answer is hashed, the wave that
+// hashes it keeps it (no lower nonce qualifies), and its workgroup appends it when it leaves the job.
+// Every wave of the workgroup calls this at the same point; job == kNoJob appends nothing.
+__device__ __forceinline__ void first_batch_flush(uint32_t job) {
+    __syncthreads();  // every wave's hits for `job` are in LDS
+    if (threadIdx.x == 0 && job != kNoJob) {
+        const FirstState& fs = first_state();
+        unsigned long long bn = 0, bh = 0;
+        unsigned int any = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (fs.found[i] && (!any || fs.n[i] < bn)) {
+                bn = fs.n[i];
+                bh = fs.h[i];
+                any = 1;
+            }
+        }
+        if (any) {
+            BatchState& bs = batch_state();
+            const unsigned int idx = atomicAdd(bs.count, 1u);
+            if (idx < bs.count[1]) {
+                BatchEntry* const e = bs.list + idx;
+                e->hash = bh;
+                e->nonce = bn;
+                e->job = job;
+            }
+        }
+    }
+}
+
+// MODE 5, at a skipped part of descriptor i: how far the work counter may move.  Every later part
+// of descriptor i lies above its job's bound (k_scan); wave 0 looks at the up to 64 descriptors
+// after it as well, one per lane, and takes with it the unbroken run of those whose EVERY nonce
+// lies above their own job's bound (desc_min_nonce against that job's word, read here): once the
+// low digit counts have answered most jobs, a launch of a higher digit count is descriptors of
+// this kind end to end, and moving the counter one descriptor per grab made such a launch cost
+// 20 us per descriptor.  The same rule as the part's, applied to whole descriptors:
+// a job's bound never drops below its answer, so nothing at or below an answer is left out.
+// Returns the end position of the last descriptor taken; called by wave 0 only, all 64 lanes.
+template <int C2>
+__device__ __forceinline__ unsigned long long first_batch_drain_end(const LaunchDesc* __restrict__ descs,
+                                                                    const unsigned long long* __restrict__ offs,
+                                                                    int ndesc, int i) {
+    const int k = i + 1 + (int)(threadIdx.x & 63u);
+    bool above = false;
+    if (k < ndesc) {
+        const LaunchDesc& N = descs[k];
+        const unsigned long long b =
+            __hip_atomic_load(batch_state().thresh + 2ull * N.job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        above = desc_min_nonce(N, C2) > b;
+    }
+    const unsigned long long m = ~__builtin_amdgcn_ballot_w64(above);
+    const int run = m ? __builtin_ctzll(m) : 64;
+    return offs[i + 1 + run];
+}
+
 // The descriptor that owns position x: the largest i with offs[i] <= x (offs[0] = 0 and the
 // offsets rise strictly).  A workgroup's positions only rise, so the search starts from the
 // hint, the descriptor of a previous part: usually it is that one or the next, else a binary
@@ -507,7 +582,7 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
                 unsigned long long n = (D.base + (unsigned long long)p * D.R + r) * D.stride + D.tail;
                 dump[n - dump_lo] = ((unsigned long long)H0 << 32) | H1;
             }
-        } else if constexpr (MODE == 2) {
+        } else if constexpr (MODE == 2 || MODE == 5) {
             // first hit: the same wave-uniform prune, against the target's high word
             // (dump_lo carries the target); the rare slow path tests all 64 bits
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
@@ -714,7 +789,7 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
 #endif
         if constexpr (MODE == 1) {
             if (lane_ok) dump[D.base + (unsigned long long)r * D.RQ + x - dump_lo] = ((unsigned long long)H0 << 32) | H1;
-        } else if constexpr (MODE == 2) {
+        } else if constexpr (MODE == 2 || MODE == 5) {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // first hit: as scan_row's MODE 2
                 m = __builtin_amdgcn_ballot_w64(H0 <= wb.T && lane_ok);
@@ -774,6 +849,16 @@ __device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return ((unsigned long long)hi << 32) | lo;
+}
+
+// a < b for wave-uniform 64-bit values, as scalar compares of the halves.  A 64-bit less-than is a
+// VALU instruction here and keeps a VGPR copy of an operand that outlives the per-nonce loop alive
+// through it (the plain kernels have none to spare: at J = 13 the pair went to scratch); the empty
+// asm keeps the halves from being re-joined.
+__device__ __forceinline__ bool uniform_lt64(unsigned long long a, unsigned long long b) {
+    uint32_t ah = (uint32_t)(a >> 32), al = (uint32_t)a, bh = (uint32_t)(b >> 32), bl = (uint32_t)b;
+    asm volatile("" : "+s"(ah), "+s"(al), "+s"(bh), "+s"(bl));
+    return ah < bh || (ah == bh && al < bl);
 }
 
 // Persistent scan over every launch descriptor of one kernel variant.
@@ -851,7 +936,25 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         if (tid == 0) { bs.job = kNoJob; bs.idx = 0u; }
         __syncthreads();
     }
+    if constexpr (MODE == 5) {  // thresh, cands, ncand: see first_batch_flush
+        BatchState& bs = batch_state();
+        FirstState& fs = first_state();
+        if (tid == 0) {
+            bs.thresh = thresh;
+            bs.list = reinterpret_cast<BatchEntry*>(cands);
+            bs.count = ncand;
+            bs.job = kNoJob;
+            bs.idx = 0u;
+            fs.grab_bound = ~0ull;  // no job yet: the first part changes to one
+        }
+        if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
+        __syncthreads();
+    }
     for (;;) {
+        // MODE 5 keeps the bound of the grab in LDS alone (grab_bound) and every wave reads it
+        // back at each part: no wave may still be among the parts of the last piece when thread 0
+        // overwrites it
+        if constexpr (MODE == 5) __syncthreads();
         if (tid == 0) {
             const unsigned long long cur = __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long rem = cur < total ? total - cur : 0ull;
@@ -861,6 +964,12 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             sh_grab[1] = g;
             if constexpr (MODE == 2)  // the bound of this grab, broadcast with the grab itself
                 first_state().grab_bound = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (MODE == 5) {  // the same, of the job the workgroup is in
+                const uint32_t cur = batch_state().job;
+                if (cur != kNoJob)
+                    first_state().grab_bound =
+                        __hip_atomic_load(thresh + 2ull * cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         __syncthreads();
         unsigned long long x = uniform64(sh_grab[0]);
@@ -868,8 +977,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         unsigned long long grab_bound = ~0ull;
         if constexpr (MODE == 2) grab_bound = uniform64(first_state().grab_bound);
         __syncthreads();
-        if (x >= total) break;
-        const unsigned long long end = x + g < total ? x + g : total;
+        unsigned long long end;
+        if constexpr (MODE == 5) {  // the same two tests, on the scalar unit
+            if (!uniform_lt64(x, total)) break;
+            end = uniform_lt64(x + g, total) ? x + g : total;
+        } else {
+            if (x >= total) break;
+            end = x + g < total ? x + g : total;
+        }
         if constexpr (MODE == 0) {
             const unsigned long long tv = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)(tv >> 32));
@@ -896,6 +1011,8 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         // The bound is held and compared as two 32-bit halves, scalar compares both: a 64-bit
         // compare is a VALU instruction here and would keep a VGPR copy of the bound alive
         // through the per-nonce loop (the empty asm keeps the halves from being re-joined).
+        // (MODE 5 reads the halves back from LDS at every part instead: with MODE 4's descriptor
+        // index live as well, the pair held across the loop spilled two VGPRs at J = 13.)
         uint32_t bound_hi = ~0u, bound_lo = ~0u;
         if constexpr (MODE == 2) {
             bound_hi = (uint32_t)(grab_bound >> 32);
@@ -904,7 +1021,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         }
         while (x < end) {
             int i = 0;
-            if constexpr (MODE == 4) {  // thousands of descriptors per group: no linear walk
+            if constexpr (MODE == 4 || MODE == 5) {  // thousands of descriptors per group: no linear walk
                 i = batch_find(offs, ndesc, x);
                 // held as a scalar from here on: without this LLVM moves part of the loop's
                 // uniform ascii4(r) onto the VALU (+4 VALU instructions per nonce at J = 4)
@@ -927,11 +1044,41 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                     wb = WaveBest{~0ull, ~0ull, batch_T(job)};
                 }
             }
+            if constexpr (MODE == 5) {
+                // a part of another job: append the hit for the current one, then the new job's
+                // bound and target.  Thread 0 loads them between the barriers, the bound as at a
+                // grab: ONE value for the workgroup, which every wave reads from LDS at each part.
+                BatchState& bs = batch_state();
+                const uint32_t job = __builtin_amdgcn_readfirstlane(D.job);
+                const uint32_t cur = __builtin_amdgcn_readfirstlane(bs.job);
+                if (job != cur) {
+                    first_batch_flush(cur);
+                    FirstState& fs = first_state();
+                    if (tid == 0) {
+                        unsigned long long* const words = bs.thresh + 2ull * job;
+                        bs.job = job;
+                        fs.bound = words;
+                        fs.grab_bound = __hip_atomic_load(words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        fs.target = __hip_atomic_load(words + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                        for (int w = 0; w < 4; w++) fs.found[w] = 0u;
+                    }
+                    __syncthreads();
+                    wb.T = __builtin_amdgcn_readfirstlane((uint32_t)(fs.target >> 32));
+                }
+            }
             const uint32_t row = rel / D.R, r0 = rel - row * D.R;
             const unsigned long long left = end - x;
             const uint32_t r1 = (unsigned long long)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
-            if constexpr (MODE == 2) {
-                const unsigned long long lb = part_min_nonce(D, C2, row, r0);
+            if constexpr (MODE == 2 || MODE == 5) {
+                unsigned long long lb = part_min_nonce(D, C2, row, r0);
+                if constexpr (MODE == 5) {  // never below the descriptor's first nonce (plan.h)
+                    const unsigned long long dl = desc_min_nonce(D, C2);
+                    lb = lb < dl ? dl : lb;
+                    const unsigned long long gb = uniform64(first_state().grab_bound);
+                    bound_hi = (uint32_t)(gb >> 32);
+                    bound_lo = (uint32_t)gb;
+                }
                 const uint32_t lh = (uint32_t)(lb >> 32), ll = (uint32_t)lb;
                 if (lh > bound_hi || (lh == bound_hi && ll > bound_lo)) {  // lb > bound
                     if constexpr (C2 != 3) {
@@ -946,7 +1093,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                         // no nonce of the range (plan.h), so cancelling it loses nothing; this
                         // part's own value, being above the bound, has not wrapped below it.
                         const unsigned long long dend = offs[i + 1];
-                        if (tid == 0) atomicMax(work, dend);
+                        if constexpr (MODE == 5) {  // and the descriptors after it that drain whole
+                            if (tid < 64u) {
+                                const unsigned long long far = first_batch_drain_end<C2>(descs, offs, ndesc, i);
+                                if (tid == 0) atomicMax(work, far);
+                            }
+                        } else {
+                            if (tid == 0) atomicMax(work, dend);
+                        }
                         x = dend < end ? dend : end;
                     } else {
                         x += r1 - r0;  // lane table: the next row starts lower again
@@ -989,6 +1143,8 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         const uint32_t cur = __builtin_amdgcn_readfirstlane(batch_state().job);
         if (cur != kNoJob) batch_flush(wb, cur, sh_best);
     }
+    if constexpr (MODE == 5)  // leave the last job
+        first_batch_flush(__builtin_amdgcn_readfirstlane(batch_state().job));
     if constexpr (MODE == 2) {
         // the workgroup's lowest-nonce hit, appended only if it has one (the host reads
         // "found" off the append counter).  The pair is stored SWAPPED, nonce in .hash, so

@@ -62,7 +62,8 @@ struct StageGroup {
     std::vector<size_t> idx;  // its launches in Stage::plan, in plan order
     uint64_t total = 0;       // row-iterations (offs[n])
     uint64_t nonces = 0;      // of all its launches
-    int d = 0, c = 0;         // digits and digit blocks of its largest launch (the first such)
+    int d = 0, c = 0;         // digits and digit blocks of its largest launch (the first such);
+                              // a first-hit batch stage: the digit count of all of them
     // byte positions in the metadata buffer, each 16-byte aligned: the counter block, the
     // n + 1 prefix offsets (8 B each), the n descriptors, and for C2 = 3 the launches' p-tables
     size_t work_at = 0, offs_at = 0, desc_at = 0, ptab_at = 0, ptab_bytes = 0;
@@ -79,7 +80,7 @@ struct StageTab {
     size_t launch = 0;  // that descriptor's launch in Stage::plan
 };
 
-// One search of a batch (gpuhash_min_batch).
+// One search of a batch (gpuhash_min_batch, gpuhash_first_below_batch).
 struct BatchJob {
     const uint8_t* msg;
     uint64_t len, lo, hi;
@@ -105,8 +106,11 @@ inline uint64_t batch_job_entries(uint64_t span, uint32_t gmin, uint64_t grid) {
 
 // The metadata bytes a job adds to a batch stage, at most (every alignment gap at its widest):
 // what the sub-batch cut (gpuhash.h) sums, with the K+W tables the job adds (BatchTables).
-inline uint64_t batch_job_bytes(const std::vector<Launch>& plan, uint32_t gmin) {
-    uint64_t b = 8 + 16;  // its pruning word; its share of the list head
+// A first-hit batch (pair) has two words per job, and may put every launch in a group of its own:
+// the group's second prefix offset then takes 8 of the 64 bytes priced for the gaps, which are
+// at most 15 wide there (the offsets and the descriptors end 16-byte aligned).
+inline uint64_t batch_job_bytes(const std::vector<Launch>& plan, uint32_t gmin, bool pair = false) {
+    uint64_t b = (pair ? 16 : 8) + 16;  // its pruning word (pair: bound and target); its share of the list head
     for (const Launch& l : plan) {
         b += sizeof(LaunchDesc) + 8 + kCounterBytes + 4 * 16;
         b += sizeof(uint32_t) * l.nptab;
@@ -146,11 +150,12 @@ struct PlannedJob {
     double cost;
 };
 
-inline PlannedJob plan_job(const BatchJob& j, uint32_t rchunk, int policy, bool host_ptab = false) {
+inline PlannedJob plan_job(const BatchJob& j, uint32_t rchunk, int policy, bool host_ptab = false,
+                           bool pair = false) {
     PlannedJob p;
     plan_range(j.msg, j.len, j.lo, j.hi, p.plan, rchunk, policy, host_ptab);
     const uint32_t gmax = rchunk ? rchunk : kDefaultMaxPiece;
-    p.bytes = batch_job_bytes(p.plan, std::min(kMinPiece, gmax));
+    p.bytes = batch_job_bytes(p.plan, std::min(kMinPiece, gmax), pair);
     p.cost = plan_cost(p.plan);
     return p;
 }
@@ -225,6 +230,18 @@ struct Stage {
     // list_at: kBatchListHead bytes of append counter, then room for list_cap BatchEntry.
     // Only the first upload_bytes bytes are host-built (a single stage: all of them).
     size_t njobs = 0, thresh_at = 0, list_at = 0, list_cap = 0, upload_bytes = 0;
+    // A first-hit batch stage (gpuhash_first_below_batch; by_digits): a batch stage whose groups
+    // are keyed (d, J, C2, EX), d the launches' digit count, and ordered by d ascending, then by
+    // first appearance.  The groups run back to back on one stream, so every nonce of up to d
+    // digits of every job has been hashed, and its hit published in the job's bound word, before
+    // any launch of more than d digits starts: A JOB WHOSE ANSWER HAS d DIGITS NEVER HASHES A
+    // NONCE OF MORE THAN d DIGITS.  That is a property of this order alone, whatever the
+    // workgroups' timing (the kernel's MODE 5 reads the bound at a job change and skips every part
+    // whose nonces all lie above it).  The per-job region at thresh_at holds TWO 64-bit words per
+    // job: the bound, the lowest qualifying nonce found so far (armed to all ones), then the job's
+    // target.  The result list is a batch stage's.
+    bool by_digits = false;
+    std::vector<uint64_t> targets;  // by_digits: one per job
 
     Stage(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy,
           bool host_ptab = false) : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)) {
@@ -245,18 +262,39 @@ struct Stage {
         lay_out();
     }
 
+    // The stage of a first-hit batch: plans[k] as above, target[k] job k's target.  See by_digits.
+    Stage(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk)
+        : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()),
+          by_digits(true), targets(target, target + plans.size()) {
+        for (size_t k = 0; k < plans.size(); k++)
+            for (Launch& l : plans[k]) {
+                l.desc.job = (uint32_t)k;
+                plan.push_back(std::move(l));
+            }
+        lay_out();
+    }
+
     static size_t aligned(size_t b) { return (b + 15) & ~(size_t)15; }
+
+    // Bytes of a job's words in the per-job region.
+    size_t job_words_bytes() const { return by_digits ? 16 : 8; }
 
    private:
     void lay_out() {
         for (size_t i = 0; i < plan.size(); i++) {
             const Launch& l = plan[i];
             auto it = std::find_if(groups.begin(), groups.end(), [&](const StageGroup& g) {
-                return g.J == l.J && g.C2 == l.C2 && g.EX == l.EX;
+                return g.J == l.J && g.C2 == l.C2 && g.EX == l.EX && (!by_digits || g.d == l.d);
             });
-            if (it == groups.end()) it = groups.insert(it, StageGroup{l.J, l.C2, l.EX});
+            if (it == groups.end()) {
+                it = groups.insert(it, StageGroup{l.J, l.C2, l.EX});
+                it->d = l.d;
+            }
             it->idx.push_back(i);
         }
+        if (by_digits)
+            std::stable_sort(groups.begin(), groups.end(),
+                             [](const StageGroup& a, const StageGroup& b) { return a.d < b.d; });
         auto align = [&] { bytes = aligned(bytes); };
         bytes = kCounterBytes * groups.size();
         align();
@@ -305,7 +343,7 @@ struct Stage {
         upload_bytes = bytes;
         if (!njobs) return;
         thresh_at = bytes;
-        bytes += 8 * njobs;
+        bytes += job_words_bytes() * njobs;
         align();
         list_at = bytes;
         upload_bytes = list_at + kBatchListHead;
@@ -341,7 +379,9 @@ struct Stage {
             offs[g.idx.size()] = acc;
         }
         if (njobs) {
-            std::memset(meta + thresh_at, 0xFF, 8 * njobs);
+            std::memset(meta + thresh_at, 0xFF, job_words_bytes() * njobs);
+            for (size_t k = 0; by_digits && k < njobs; k++)  // {bound: all ones, target}
+                std::memcpy(meta + thresh_at + 16 * k + 8, &targets[k], 8);
             const uint32_t head[4] = {0u, (uint32_t)list_cap, 0u, 0u};  // appended, capacity
             std::memcpy(meta + list_at, head, kBatchListHead);
         }

@@ -51,6 +51,7 @@ EXPORTED = [
     "gpuhash_first_below", "gpuhash_first_below_ex",
     "gpuhash_collect_below", "gpuhash_collect_below_ex",
     "gpuhash_min_batch", "gpuhash_min_batch_ex",
+    "gpuhash_first_below_batch", "gpuhash_first_below_batch_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
@@ -168,6 +169,15 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
     lib.gpuhash_min_batch_ex.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                          ctypes.c_uint32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.gpuhash_min_batch_ex.restype = ctypes.c_int
+    lib.gpuhash_first_below_batch.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
+                                              ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                              ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_int)]
+    lib.gpuhash_first_below_batch.restype = ctypes.c_int
+    lib.gpuhash_first_below_batch_ex.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
+                                                 ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_uint32,
+                                                 ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                 ctypes.POINTER(ctypes.c_int)]
+    lib.gpuhash_first_below_batch_ex.restype = ctypes.c_int
     lib.gpuhash_hash_range.argtypes = [vp, u8p, sz, u64, u64, vp]
     lib.gpuhash_hash_range.restype = ctypes.c_int
     lib.gpuhash_hash_cpu.argtypes = [u8p, sz, u64]
@@ -273,6 +283,19 @@ class Engine:
         in: at least one and at most GPUHASH_BATCH_MAX_JOBS jobs, bounds as for min(), lower <=
         upper, at most GPUHASH_BATCH_MAX_SPAN nonces and GPUHASH_MAX_MSG message bytes per job
         (ValueError)."""
+        n, data, off, lower, upper, _ = self._batch_arrays(jobs, rchunk, 3)
+        hashes, nonces = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        rc = self._lib.gpuhash_min_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper, rchunk,
+                                            hashes, nonces)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_min_batch")
+        return list(zip(hashes, nonces))
+
+    @staticmethod
+    def _batch_arrays(jobs, rchunk, fields):
+        """The batch calls' checks and flat arrays, for jobs of `fields` fields: (msg, lower,
+        upper), then a target when there are 4.  (njobs, msgs, msg_off, lower, upper, target)."""
+        what = "(msg, lower, upper)" if fields == 3 else "(msg, lower, upper, target)"
         jobs = [tuple(j) for j in jobs]
         if not 1 <= len(jobs) <= GPUHASH_BATCH_MAX_JOBS:
             raise ValueError(f"{len(jobs)} jobs outside [1, GPUHASH_BATCH_MAX_JOBS]")
@@ -280,9 +303,11 @@ class Engine:
             raise ValueError(f"rchunk={rchunk!r} outside [0, 2^32)")
         msgs = []
         for k, j in enumerate(jobs):
-            if len(j) != 3:
-                raise ValueError(f"job {k} is not (msg, lower, upper)")
+            if len(j) != fields:
+                raise ValueError(f"job {k} is not {what}")
             m, lo, hi = _bytes(j[0]), _check_u64(f"jobs[{k}].lower", j[1]), _check_u64(f"jobs[{k}].upper", j[2])
+            if fields == 4:
+                _check_u64(f"jobs[{k}].target", j[3])
             if lo > hi:
                 raise ValueError(f"jobs[{k}]: lower={lo} > upper={hi}")
             if hi - lo >= GPUHASH_BATCH_MAX_SPAN:
@@ -297,12 +322,22 @@ class Engine:
         data = ctypes.create_string_buffer(b"".join(msgs), off[n] + 1)
         lower = (ctypes.c_uint64 * n)(*[j[1] for j in jobs])
         upper = (ctypes.c_uint64 * n)(*[j[2] for j in jobs])
-        hashes, nonces = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
-        rc = self._lib.gpuhash_min_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper, rchunk,
-                                            hashes, nonces)
+        target = (ctypes.c_uint64 * n)(*[j[3] for j in jobs]) if fields == 4 else None
+        return n, data, off, lower, upper, target
+
+    def first_below_batch(self, jobs, rchunk: int = 0) -> list[tuple[int, int] | None]:
+        """Many independent first-hit searches in one call: entry k is what first_below(*jobs[k])
+        returns, (hash, nonce) of the lowest nonce whose hash is <= the job's target or None, for
+        jobs given as (msg, lower, upper, target) (gpuhash_first_below_batch_ex; one scan launch
+        per digit count and kernel variant among all the jobs, in ascending digit order).  Jobs
+        are checked before calling in, as for min_batch (ValueError, TypeError)."""
+        n, data, off, lower, upper, target = self._batch_arrays(jobs, rchunk, 4)
+        hashes, nonces, found = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)(), (ctypes.c_int * n)()
+        rc = self._lib.gpuhash_first_below_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper, target,
+                                                    rchunk, hashes, nonces, found)
         if rc != GPUHASH_OK:
-            raise GpuHashError(rc, "gpuhash_min_batch")
-        return list(zip(hashes, nonces))
+            raise GpuHashError(rc, "gpuhash_first_below_batch")
+        return [(int(hashes[k]), int(nonces[k])) if found[k] else None for k in range(n)]
 
     def first_below(self, msg, lower: int, upper: int, target: int, rchunk: int = 0) -> tuple[int, int] | None:
         """(hash, nonce) of the LOWEST nonce n of the inclusive [lower, upper] with

@@ -282,6 +282,39 @@ int gpuhash_min_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *ms
                          const uint64_t *lower, const uint64_t *upper, uint32_t rchunk,
                          uint64_t *out_hashes, uint64_t *out_nonces);
 
+/* njobs independent gpuhash_first_below searches in one call (a service that mints one
+ * proof-of-work stamp per request): out_found[k], and when it is 1 (out_hashes[k], out_nonces[k]),
+ * are exactly what gpuhash_first_below(ctx, msg_k, len_k, lower[k], upper[k], target[k], ...)
+ * returns -- the LOWEST nonce of the job's range whose hash is <= target[k], and its hash -- under
+ * every layout policy, tail flag and rchunk, however many context entries ran and in whatever order
+ * the jobs are listed.  A job with out_found[k] == 0 leaves its two outputs untouched.  The
+ * comparison is <=, and a nonce of 2^64-1 is a legal answer.  The jobs are independent: two jobs of
+ * one message with different targets or overlapping ranges are two searches.
+ * A gpuhash_first_below call costs ~0.4 ms however early its hit lies; a batch runs one scan
+ * launch per DIGIT COUNT per kernel variant among all its jobs, in ascending digit order, so a
+ * job whose answer has d digits never hashes a nonce of more than d digits, and skips within its
+ * digit count as gpuhash_first_below does.
+ * The flat arrays, msg_off, the whole-call argument errors (detected before any use of ctx's
+ * contents and before anything is written to the outputs; a null target or out_found is
+ * GPUHASH_EINVAL too), GPUHASH_BATCH_MAX_JOBS, GPUHASH_BATCH_MAX_SPAN, the sub-batches under
+ * GPUHASH_BATCH_BYTES and the runs of whole jobs over the context's entries are as for
+ * gpuhash_min_batch.
+ * Afterwards gpuhash_last_stats().nonces is the saturating sum over the jobs of what an ascending
+ * scan would have examined -- nonce - lower + 1 when found, the span otherwise -- and .launches
+ * the scan launches that ran; gpuhash_last_launches gives one record per (digits, kernel variant)
+ * per context entry per sub-batch, in launch order, with `digits` exact, `nonces` the total the
+ * launch covers (not what it hashed) and `lo`, `hi` job indices as for gpuhash_min_batch.
+ * Threading, device-guard behaviour, errors and the no-exception rule are as for gpuhash_min.
+ * Replaces nothing in the reference (its protocol has no target field). */
+int gpuhash_first_below_batch(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                              const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
+                              uint64_t *out_hashes, uint64_t *out_nonces, int *out_found);
+
+/* Same batch, caller-chosen work-item granularity (as gpuhash_min_ex). */
+int gpuhash_first_below_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                                 const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
+                                 uint32_t rchunk, uint64_t *out_hashes, uint64_t *out_nonces, int *out_found);
+
 /* out[i] = Hash(msg, lower + i) for i < count, computed on the first device by the
  * SAME kernels as gpuhash_min (per-nonce dump mode).  count <= 2^26; lower + count - 1
  * must not wrap.  Parity/diagnostic API (batch form of hash.go:11-15). */

@@ -182,5 +182,47 @@ func (e *Engine) MinBatch(jobs []Job) (hashes, nonces []uint64, err error) {
 	return hashes, nonces, nil
 }
 
+// FirstBelowBatch answers many independent first-hit searches in one call: found[k], and when
+// it is true hashes[k], nonces[k], are exactly what FirstBelow(jobs[k].Data, jobs[k].Lower,
+// jobs[k].Upper, targets[k]) returns -- the lowest nonce whose hash is at or below the target.
+// For a service that mints one proof-of-work stamp per request: the engine runs one kernel
+// launch per digit count and kernel variant among all the jobs, in ascending digit order, so
+// a job with an early hit costs next to nothing, where a loop of FirstBelow calls pays
+// ~0.4 ms per call.  len(targets) must equal len(jobs); the limits are MinBatch's.
+func (e *Engine) FirstBelowBatch(jobs []Job, targets []uint64) (hashes, nonces []uint64, found []bool, err error) {
+	n := len(jobs)
+	if n == 0 || n > int(C.GPUHASH_BATCH_MAX_JOBS) || len(targets) != n {
+		return nil, nil, nil, rcErr(C.GPUHASH_EINVAL)
+	}
+	off := make([]C.size_t, n+1)
+	lower := make([]C.uint64_t, n)
+	upper := make([]C.uint64_t, n)
+	target := make([]C.uint64_t, n)
+	msgs := make([]byte, 0, 64*n)
+	for k, j := range jobs {
+		msgs = append(msgs, j.Data...)
+		off[k+1] = C.size_t(len(msgs))
+		lower[k] = C.uint64_t(j.Lower)
+		upper[k] = C.uint64_t(j.Upper)
+		target[k] = C.uint64_t(targets[k])
+	}
+	var p *C.uint8_t
+	if len(msgs) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&msgs[0]))
+	}
+	hashes = make([]uint64, n)
+	nonces = make([]uint64, n)
+	f := make([]C.int, n)
+	rc := C.gpuhash_first_below_batch(e.ctx, p, &off[0], C.size_t(n), &lower[0], &upper[0], &target[0], (*C.uint64_t)(unsafe.Pointer(&hashes[0])), (*C.uint64_t)(unsafe.Pointer(&nonces[0])), &f[0])
+	if err = rcErr(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	found = make([]bool, n)
+	for k := range f {
+		found[k] = f[k] != 0
+	}
+	return hashes, nonces, found, nil
+}
+
 // Close releases the devices.
 func (e *Engine) Close() { C.gpuhash_close(e.ctx) }
