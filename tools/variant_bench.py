@@ -2,7 +2,11 @@
 """Times each tools/variants/<name>/libgpuhash.so (tools/build_variants.sh) on config 2
 (bradfitz, 2^32 nonces) and config 3's 10^9 window, one subprocess per variant (each
 loads its own code object), interleaved over rounds so clock drift hits all alike.
-Checks every variant returns the same (hash, nonce)."""
+Checks every variant returns the same (hash, nonce).
+  variant_bench.py [rounds [names]]     VCASES=c2,j2 limits the cases
+VBASE=<variant> adds the A/B verdict of every other variant against that one, per case: the
+gain of the means of the rounds, against a margin of three times the spread (max - min) of the
+base's own rounds, and whether the in-kernel clocks of the two lie within 1%."""
 import json
 import os
 import subprocess
@@ -24,6 +28,9 @@ with gpuhash.Engine([0], lib_path=sys.argv[1]) as e:
              ("ex", b"x" * 44, 10**11, 10**11 + (1 << 30)),        # EX (extra padding block)
              ("j13", b"y" * 44, 10**9, 10**9 + (1 << 31)),         # plain, late loop word
              ("j2", b"", 10**9, 10**9 + (1 << 31)),                # plain, early loop word
+             ("j5", b"f" * 12, 10**9, 10**9 + (1 << 31)),          # plain, J = 5 (config 4's kernel)
+             ("j9", b"n" * 28, 10**9, 10**9 + (1 << 31)),          # plain, J = 9
+             *[("j%d" % j, b"p" * (4 * j - 8), 10**9, 10**9 + (1 << 31)) for j in (3, 7, 8, 10, 11, 12)],  # plain, the other J >= 2
              ("cj1", b"c" * 61, 10**9, 10**9 + (1 << 31)),         # classic straddle C2=1, J=1
              ("u2f", b"u" * 58, 10240 * 10**7, 10240 * 10**7 + 256 * 10**7 - 1),  # C2=2, one full row
              ("u2p", b"u" * 60, 10**9, (1 << 32) - 1),  # C2=2, 430 lane values: wave 3 of row 2 idle
@@ -72,3 +79,23 @@ for n, ds in results.items():
     ref = ref or res
     best = {k: round(max(d[k]["GHs"] for d in ds), 3) for k in ds[0]}
     print(json.dumps({"variant": n, "best": best, "same_results": res == ref}), flush=True)
+base = os.environ.get("VBASE")
+if base and results.get(base):
+    mean = lambda xs: sum(xs) / len(xs)
+    for case in results[base][0]:
+        b = [d[case]["GHs"] for d in results[base]]
+        bclk = mean([d[case]["sclk"] for d in results[base]])
+        margin = 3 * (max(b) - min(b))
+        for n, ds in results.items():
+            if n == base or not ds:
+                continue
+            v = [d[case]["GHs"] for d in ds]
+            vclk = mean([d[case]["sclk"] for d in ds])
+            gain = mean(v) - mean(b)
+            print(json.dumps({"case": case, "variant": n, "base": base, "rounds": len(v),
+                              "base_mean": round(mean(b), 4), "base_min": round(min(b), 4), "base_max": round(max(b), 4),
+                              "mean": round(mean(v), 4), "min": round(min(v), 4), "max": round(max(v), 4),
+                              "gain": round(gain, 4), "gain_pct": round(100 * gain / mean(b), 3),
+                              "margin_3x_base_spread": round(margin, 4), "clears_margin": gain > margin,
+                              "sclk_mhz": [round(bclk, 1), round(vclk, 1)],
+                              "clocks_within_1pct": abs(vclk - bclk) <= 0.01 * bclk}), flush=True)
