@@ -1,9 +1,5 @@
 // kernels.hip -- launch dispatch for the gfx950 scan kernels (instantiated in
-// kernels_{plain,ut,misc}.hip, their first-hit MODE 2 instances in
-// kernels_{plain,ut,misc}_first.hip and their collecting MODE 3 instances in
-// kernels_{plain,ut,misc}_collect.hip and their batch MODE 4 instances in
-// kernels_{plain,ut,misc}_batch.hip and their first-hit batch MODE 5 instances in
-// kernels_{plain,ut,misc}_firstbatch.hip; see scan_decl.h) and the candidate reduce.
+// kernels_{plain,ut,misc}.hip, once per mode group; see scan_decl.h) and the candidate reduce.
 #include <atomic>
 
 #include "kernels.h"
@@ -47,11 +43,6 @@ __global__ __launch_bounds__(1024) void k_reduce(Cand* __restrict__ cands,
 }
 
 template <int J, int C2, bool EX, int MODE>
-static auto kfn() {
-    return &k_scan<J, C2, EX, MODE>;
-}
-
-template <int J, int C2, bool EX, int MODE>
 static hipError_t go(const ScanArgs& a) {
     hipLaunchKernelGGL((k_scan<J, C2, EX, MODE>), dim3(a.grid), dim3(256), 0, a.stream, a.descs,
                        a.offs, a.ndesc, a.work, a.gmin, a.gmax, a.thresh, a.cands, a.ncand, a.dump,
@@ -68,7 +59,7 @@ static unsigned int occ(int device) {
     unsigned int v = cache[device].load(std::memory_order_relaxed);
     if (!v) {
         int nb = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kfn<J, C2, EX, MODE>(), 256, 0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)&k_scan<J, C2, EX, MODE>, 256, 0) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
             return 0;
         v = (unsigned int)(nb > 0 ? nb : 1) * (unsigned int)cus;
@@ -132,23 +123,27 @@ struct Occupancy {
     unsigned int operator()() const { return occ<J, C2, EX, MODE>(device); }
 };
 
+// Expands a runtime mode as well.  A value that names no ScanMode lands on the dump kernel.
+template <class F>
+static auto with_mode(int J, int C2, int EX, int mode, F&& f) {
+    switch (mode) {
+        case kScanMin: return with_variant<kScanMin>(J, C2, EX, f);
+        case kScanFirst: return with_variant<kScanFirst>(J, C2, EX, f);
+        case kScanCollect: return with_variant<kScanCollect>(J, C2, EX, f);
+        case kScanBatch: return with_variant<kScanBatch>(J, C2, EX, f);
+        case kScanFirstBatch: return with_variant<kScanFirstBatch>(J, C2, EX, f);
+        default: return with_variant<kScanDump>(J, C2, EX, f);
+    }
+}
+
 unsigned int grid_for(int J, int C2, int EX, int mode, int device) {
     if (!valid_variant(J, C2, EX)) return 0;
-    if (mode == 5) return with_variant<5>(J, C2, EX, Occupancy{device});
-    if (mode == 4) return with_variant<4>(J, C2, EX, Occupancy{device});
-    if (mode == 3) return with_variant<3>(J, C2, EX, Occupancy{device});
-    if (mode == 2) return with_variant<2>(J, C2, EX, Occupancy{device});
-    return mode == 0 ? with_variant<0>(J, C2, EX, Occupancy{device})
-                     : with_variant<1>(J, C2, EX, Occupancy{device});
+    return with_mode(J, C2, EX, mode, Occupancy{device});
 }
 
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a) {
     if (!valid_variant(J, C2, EX) || a.grid == 0 || a.ndesc <= 0) return hipErrorInvalidValue;
-    if (mode == 5) return with_variant<5>(J, C2, EX, Launcher{a});
-    if (mode == 4) return with_variant<4>(J, C2, EX, Launcher{a});
-    if (mode == 3) return with_variant<3>(J, C2, EX, Launcher{a});
-    if (mode == 2) return with_variant<2>(J, C2, EX, Launcher{a});
-    return mode == 0 ? with_variant<0>(J, C2, EX, Launcher{a}) : with_variant<1>(J, C2, EX, Launcher{a});
+    return with_mode(J, C2, EX, mode, Launcher{a});
 }
 
 hipError_t launch_ktab(const LaunchDesc* d_desc, uint32_t* tab, uint32_t R, hipStream_t stream) {

@@ -1,11 +1,13 @@
 // kernels_ut.hip -- k_scan instances of the K+W-table uniform-schedule layout (C2 = 1,
-// J = 0: block B holds loop digits only), the lane-table layout (C2 = 3,
-// J = 1) and the table builder k_ktab.
+// J = 0: block B holds loop digits only) and the lane-table layout (C2 = 3,
+// J = 1), for the mode group of this compile (scan_decl.h); the table builders
+// k_ktab and k_ptab go with MODE 0 and 1.
 // Built with -mllvm -amdgpu-sched-strategy=max-ilp (Makefile): +2.1% on config 3 over
 // the default options (profiles/r01_variants.jsonl).
 #include "scan_decl.h"
 #include "scan_kernel.h"
 
+#ifndef GPUHASH_MODE
 namespace gpuhash {
 
 // Uniform schedule table of a C2/J=0 descriptor (one thread per loop value r):
@@ -58,9 +60,8 @@ __global__ __launch_bounds__(256) void k_ptab(const LaunchDesc* __restrict__ des
 }
 
 }  // namespace gpuhash
+#endif
 
-GPUHASH_INSTANTIATE_SCAN(0, 1, false, 0);
-GPUHASH_INSTANTIATE_SCAN(0, 1, false, 1);
 // C2 = 3: the lane-table straddle layout (scan_row_lt), uniform-table family too
-GPUHASH_INSTANTIATE_SCAN(1, 3, false, 0);
-GPUHASH_INSTANTIATE_SCAN(1, 3, false, 1);
+#define GPUHASH_UT_LAYOUTS(X) X(0, 1, false) X(1, 3, false)
+GPUHASH_UT_LAYOUTS(GPUHASH_INSTANTIATE_LAYOUT)

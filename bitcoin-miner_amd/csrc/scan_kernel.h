@@ -22,36 +22,32 @@
 // north_star).  The pruning is exact: T only ever holds the high word of a hash some
 // valid nonce already achieved, and ties on the high word take the slow path.
 //
-// MODE 2 is the other question, gpuhash_first_below: the LOWEST nonce whose hash is at or
-// below a target.  Per nonce it costs what MODE 0 costs (the same v_cmp and ballot, T = the
+// MODE 2 (kScanFirst) is the other question, gpuhash_first_below: the LOWEST nonce whose hash is
+// at or below a target.  Per nonce it costs what MODE 0 costs (the same v_cmp and ballot, T = the
 // target's high word); the word `thresh` points to holds the lowest qualifying nonce found
 // so far, and parts of the work that lie wholly above it are skipped unhashed (k_scan, at
-// the grab).  Its instances live in kernels_*_first.hip; MODE 0 and MODE 1 compile to the
-// same machine code with or without it.
+// the grab).
 //
-// MODE 3 is the third, gpuhash_collect_below: EVERY nonce whose hash is at or below a target,
-// counted exactly and listed while the device list has room (CollectState, below).  The same
-// per-nonce compare and ballot; the slow path appends.  Its instances live in
-// kernels_*_collect.hip, and MODE 0, 1 and 2 compile to the same machine code with or
-// without it.
+// MODE 3 (kScanCollect) is the third, gpuhash_collect_below: EVERY nonce whose hash is at or below
+// a target, counted exactly and listed while the device list has room (CollectState, below).  The
+// same per-nonce compare and ballot; the slow path appends.
 //
-// MODE 4 is MODE 0 for a batch of independent jobs, gpuhash_min_batch (BatchState, below).  Its
-// instances live in kernels_*_batch.hip, and the other modes compile to the same machine code
-// with or without it.
+// MODE 4 (kScanBatch) is MODE 0 for a batch of independent jobs, gpuhash_min_batch (BatchState,
+// below).
 //
-// MODE 5 is MODE 2 for a batch of independent jobs, gpuhash_first_below_batch: MODE 2's per-nonce
-// test, slow path, skip and drain rules against the CURRENT JOB's bound and target, and MODE 4's
-// descriptor lookup, job change and result list (first_batch_flush, below).  Its instances live in
-// kernels_*_firstbatch.hip, and the other modes compile to the same machine code with or without
-// it.
+// MODE 5 (kScanFirstBatch) is MODE 2 for a batch of independent jobs, gpuhash_first_below_batch:
+// MODE 2's per-nonce test, slow path, skip and drain rules against the CURRENT JOB's bound and
+// target, and MODE 4's descriptor lookup, job change and result list (first_batch_flush, below).
+//
+// Every mode group is a code object of its own (scan_decl.h), and each mode compiles to the same
+// machine code whatever the others hold: tests/golden/kernel_manifest.txt pins every kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
-#include "kernels.h"
-#include "plan.h"
+#include "scan_decl.h"
 
 // Code phase of the per-nonce loop bodies.  The same instruction stream runs ~3.5% faster
 // when the loop body starts at 4 mod 8 bytes than at 0 mod 8 (measured on config 2, J = 2,
@@ -73,6 +69,11 @@
 #endif
 
 namespace gpuhash {
+
+// MODE is a ScanMode (kernels.h).  The first-hit modes share the per-nonce test and the skip
+// rule, the batch modes the descriptor lookup and the result list.
+constexpr bool is_first_mode(int mode) { return mode == kScanFirst || mode == kScanFirstBatch; }
+constexpr bool is_batch_mode(int mode) { return mode == kScanBatch || mode == kScanFirstBatch; }
 
 namespace dev {
 
@@ -321,6 +322,15 @@ __device__ __forceinline__ BatchState& batch_state() {
     __shared__ BatchState bs;
     return bs;
 }
+// The state at the start of a launch, from k_scan's arguments: no job yet.  Thread 0 alone.
+__device__ __forceinline__ void batch_arm(unsigned long long* thresh, Cand* cands, unsigned int* ncand) {
+    BatchState& bs = batch_state();
+    bs.thresh = thresh;
+    bs.list = reinterpret_cast<BatchEntry*>(cands);
+    bs.count = ncand;
+    bs.job = kNoJob;
+    bs.idx = 0u;
+}
 
 // The pruning word of `job`, its high half: the T to arm or tighten a WaveBest with.
 __device__ __forceinline__ uint32_t batch_T(uint32_t job) {
@@ -331,6 +341,9 @@ __device__ __forceinline__ uint32_t batch_T(uint32_t job) {
 
 // Leaves `job`: the workgroup's best for it, one list entry if it has any.  Every wave of the
 // workgroup calls this at the same point.
+// (The four-wave fold below is also the end of k_scan for MODE 0, and first_batch_flush's is the
+// end for MODE 2, as copies: a shared helper -- with out-parameters, a returned struct or a
+// callback -- changed the register assignment of one user or the other each time it was tried.)
 __device__ __forceinline__ void batch_flush(const WaveBest& wb, uint32_t job,
                                             unsigned long long (&sh_best)[4][2]) {
     const uint32_t tid = threadIdx.x;
@@ -569,6 +582,10 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
 
     // Per-nonce bookkeeping: dump (MODE 1) or the exact lexicographic running best with
     // the wave-uniform pruning test (MODE 0).
+    // The ballot-and-readlane walk is written out per mode, here and in scan_row_lt, on purpose:
+    // sharing it (a hit_test<MODE> taking the edge predicate and the nonce formula, or the
+    // predicate inside the ballot) reordered the hot loops of 12 to 76 of the kernels when tried.
+    // Do not fold it without GPU measurements of every kernel whose code changes.
     auto finish = [&](uint32_t r, uint32_t H0, uint32_t H1) {
 #ifdef GPUHASH_TIE_TEST_BITS
         // Test-only build (libgpuhash_tietest.so): keep only the top bits of the hash so
@@ -576,13 +593,13 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
         H0 >>= (32 - GPUHASH_TIE_TEST_BITS);
         H1 = 0;
 #endif
-        if constexpr (MODE == 1) {
+        if constexpr (MODE == kScanDump) {
             if (lane_ok && r >= rlo && r <= rhi) {
                 // k = D.base + p·R + r; nonce = k·stride + tail (tail-digit launches, plan.h)
                 unsigned long long n = (D.base + (unsigned long long)p * D.R + r) * D.stride + D.tail;
                 dump[n - dump_lo] = ((unsigned long long)H0 << 32) | H1;
             }
-        } else if constexpr (MODE == 2 || MODE == 5) {
+        } else if constexpr (is_first_mode(MODE)) {
             // first hit: the same wave-uniform prune, against the target's high word
             // (dump_lo carries the target); the rare slow path tests all 64 bits
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
@@ -600,7 +617,7 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
                     first_hit(hh, nn);
                 }
             }
-        } else if constexpr (MODE == 3) {
+        } else if constexpr (MODE == kScanCollect) {
             // collect: MODE 2's prune; the slow path appends every lane that passes the
             // edge masks and the exact 64-bit test
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
@@ -787,9 +804,9 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
         H0 >>= (32 - GPUHASH_TIE_TEST_BITS);
         H1 = 0;
 #endif
-        if constexpr (MODE == 1) {
+        if constexpr (MODE == kScanDump) {
             if (lane_ok) dump[D.base + (unsigned long long)r * D.RQ + x - dump_lo] = ((unsigned long long)H0 << 32) | H1;
-        } else if constexpr (MODE == 2 || MODE == 5) {
+        } else if constexpr (is_first_mode(MODE)) {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // first hit: as scan_row's MODE 2
                 m = __builtin_amdgcn_ballot_w64(H0 <= wb.T && lane_ok);
@@ -804,7 +821,7 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
                     first_hit(hh, nn);
                 }
             }
-        } else if constexpr (MODE == 3) {
+        } else if constexpr (MODE == kScanCollect) {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // collect: as scan_row's MODE 3
                 m = collect_ballot(H0, H1, wb.T, lane_ok);
@@ -878,16 +895,7 @@ __device__ __forceinline__ bool uniform_lt64(unsigned long long a, unsigned long
 #define GPUHASH_SCAN_ATTR
 #endif
 template <int J, int C2, bool EX, int MODE>
-__global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc* __restrict__ descs,
-                                              const unsigned long long* __restrict__ offs,
-                                              int ndesc, unsigned long long* __restrict__ work,
-                                              unsigned int gmin, unsigned int gmax,
-                                              unsigned long long* __restrict__ thresh,
-                                              Cand* __restrict__ cands,
-                                              unsigned int* __restrict__ ncand,
-                                              unsigned long long* __restrict__ dump,
-                                              unsigned long long dump_lo,
-                                              const uint32_t* __restrict__ ktab) {
+__global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(GPUHASH_SCAN_PARAMS) {
     static_assert(J >= 0 && J < 16, "loop word index");
     static_assert(!C2 || J <= 1, "C2 layouts have the loop word at J <= 1");
     static_assert(C2 != 2 || J == 1, "two-word uniform loop only with the loop word at J = 1");
@@ -908,14 +916,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         clk[1] = __builtin_amdgcn_s_memrealtime();
     }
     WaveBest wb{~0ull, ~0ull, 0xFFFFFFFFu};
-    if constexpr (MODE == 2) {  // dump_lo = the target
+    if constexpr (MODE == kScanFirst) {  // dump_lo = the target
         wb.T = (uint32_t)(dump_lo >> 32);
         FirstState& fs = first_state();
         if (tid == 0) { fs.target = dump_lo; fs.bound = thresh; }
         if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
         __syncthreads();
     }
-    if constexpr (MODE == 3) {  // dump_lo = the target; thresh, cands, ncand: see CollectState
+    if constexpr (MODE == kScanCollect) {  // dump_lo = the target; thresh, cands, ncand: see CollectState
         wb.T = (uint32_t)(dump_lo >> 32);
         if (tid == 0) {
             CollectState& cs = collect_state();
@@ -926,25 +934,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         }
         __syncthreads();
     }
-    if constexpr (MODE == 4) {  // thresh, cands, ncand: see BatchState
-        BatchState& bs = batch_state();
-        if (tid == 0) {
-            bs.thresh = thresh;
-            bs.list = reinterpret_cast<BatchEntry*>(cands);
-            bs.count = ncand;
-        }
-        if (tid == 0) { bs.job = kNoJob; bs.idx = 0u; }
+    if constexpr (MODE == kScanBatch) {  // thresh, cands, ncand: see BatchState
+        if (tid == 0) batch_arm(thresh, cands, ncand);
         __syncthreads();
     }
-    if constexpr (MODE == 5) {  // thresh, cands, ncand: see first_batch_flush
-        BatchState& bs = batch_state();
+    if constexpr (MODE == kScanFirstBatch) {  // thresh, cands, ncand: see first_batch_flush
         FirstState& fs = first_state();
         if (tid == 0) {
-            bs.thresh = thresh;
-            bs.list = reinterpret_cast<BatchEntry*>(cands);
-            bs.count = ncand;
-            bs.job = kNoJob;
-            bs.idx = 0u;
+            batch_arm(thresh, cands, ncand);
             fs.grab_bound = ~0ull;  // no job yet: the first part changes to one
         }
         if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
@@ -954,7 +951,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         // MODE 5 keeps the bound of the grab in LDS alone (grab_bound) and every wave reads it
         // back at each part: no wave may still be among the parts of the last piece when thread 0
         // overwrites it
-        if constexpr (MODE == 5) __syncthreads();
+        if constexpr (MODE == kScanFirstBatch) __syncthreads();
         if (tid == 0) {
             const unsigned long long cur = __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long rem = cur < total ? total - cur : 0ull;
@@ -962,9 +959,9 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             g = g < gmin ? gmin : (g > gmax ? gmax : g);
             sh_grab[0] = atomicAdd(work, g);
             sh_grab[1] = g;
-            if constexpr (MODE == 2)  // the bound of this grab, broadcast with the grab itself
+            if constexpr (MODE == kScanFirst)  // the bound of this grab, broadcast with the grab itself
                 first_state().grab_bound = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if constexpr (MODE == 5) {  // the same, of the job the workgroup is in
+            if constexpr (MODE == kScanFirstBatch) {  // the same, of the job the workgroup is in
                 const uint32_t cur = batch_state().job;
                 if (cur != kNoJob)
                     first_state().grab_bound =
@@ -975,22 +972,22 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         unsigned long long x = uniform64(sh_grab[0]);
         const unsigned long long g = uniform64(sh_grab[1]);
         unsigned long long grab_bound = ~0ull;
-        if constexpr (MODE == 2) grab_bound = uniform64(first_state().grab_bound);
+        if constexpr (MODE == kScanFirst) grab_bound = uniform64(first_state().grab_bound);
         __syncthreads();
         unsigned long long end;
-        if constexpr (MODE == 5) {  // the same two tests, on the scalar unit
+        if constexpr (MODE == kScanFirstBatch) {  // the same two tests, on the scalar unit
             if (!uniform_lt64(x, total)) break;
             end = uniform_lt64(x + g, total) ? x + g : total;
         } else {
             if (x >= total) break;
             end = x + g < total ? x + g : total;
         }
-        if constexpr (MODE == 0) {
+        if constexpr (MODE == kScanMin) {
             const unsigned long long tv = __hip_atomic_load(thresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)(tv >> 32));
             wb.T = t < wb.T ? t : wb.T;
         }
-        if constexpr (MODE == 4) {  // the same, from the word of the job the workgroup is in
+        if constexpr (MODE == kScanBatch) {  // the same, from the word of the job the workgroup is in
             const uint32_t cur = __builtin_amdgcn_readfirstlane(batch_state().job);
             if (cur != kNoJob) {
                 const uint32_t t = batch_T(cur);
@@ -1014,14 +1011,14 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         // (MODE 5 reads the halves back from LDS at every part instead: with MODE 4's descriptor
         // index live as well, the pair held across the loop spilled two VGPRs at J = 13.)
         uint32_t bound_hi = ~0u, bound_lo = ~0u;
-        if constexpr (MODE == 2) {
+        if constexpr (MODE == kScanFirst) {
             bound_hi = (uint32_t)(grab_bound >> 32);
             bound_lo = (uint32_t)grab_bound;
             asm volatile("" : "+s"(bound_hi), "+s"(bound_lo));
         }
         while (x < end) {
             int i = 0;
-            if constexpr (MODE == 4 || MODE == 5) {  // thousands of descriptors per group: no linear walk
+            if constexpr (is_batch_mode(MODE)) {  // thousands of descriptors per group: no linear walk
                 i = batch_find(offs, ndesc, x);
                 // held as a scalar from here on: without this LLVM moves part of the loop's
                 // uniform ascii4(r) onto the VALU (+4 VALU instructions per nonce at J = 4)
@@ -1031,7 +1028,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             }
             const LaunchDesc& D = descs[i];
             const uint32_t rel = (uint32_t)(x - offs[i]);  // < rows * R <= 2^32 (plan.h)
-            if constexpr (MODE == 4) {
+            if constexpr (MODE == kScanBatch) {
                 // a part of another job: leave the current one, re-arm from the new job's word
                 BatchState& bs = batch_state();
                 const uint32_t job = __builtin_amdgcn_readfirstlane(D.job);
@@ -1044,7 +1041,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                     wb = WaveBest{~0ull, ~0ull, batch_T(job)};
                 }
             }
-            if constexpr (MODE == 5) {
+            if constexpr (MODE == kScanFirstBatch) {
                 // a part of another job: append the hit for the current one, then the new job's
                 // bound and target.  Thread 0 loads them between the barriers, the bound as at a
                 // grab: ONE value for the workgroup, which every wave reads from LDS at each part.
@@ -1070,9 +1067,9 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             const uint32_t row = rel / D.R, r0 = rel - row * D.R;
             const unsigned long long left = end - x;
             const uint32_t r1 = (unsigned long long)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
-            if constexpr (MODE == 2 || MODE == 5) {
+            if constexpr (is_first_mode(MODE)) {
                 unsigned long long lb = part_min_nonce(D, C2, row, r0);
-                if constexpr (MODE == 5) {  // never below the descriptor's first nonce (plan.h)
+                if constexpr (MODE == kScanFirstBatch) {  // never below the descriptor's first nonce (plan.h)
                     const unsigned long long dl = desc_min_nonce(D, C2);
                     lb = lb < dl ? dl : lb;
                     const unsigned long long gb = uniform64(first_state().grab_bound);
@@ -1093,7 +1090,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
                         // no nonce of the range (plan.h), so cancelling it loses nothing; this
                         // part's own value, being above the bound, has not wrapped below it.
                         const unsigned long long dend = offs[i + 1];
-                        if constexpr (MODE == 5) {  // and the descriptors after it that drain whole
+                        if constexpr (MODE == kScanFirstBatch) {  // and the descriptors after it that drain whole
                             if (tid < 64u) {
                                 const unsigned long long far = first_batch_drain_end<C2>(descs, offs, ndesc, i);
                                 if (tid == 0) atomicMax(work, far);
@@ -1118,7 +1115,7 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
         clk[2] = __builtin_amdgcn_s_memtime();
         clk[3] = __builtin_amdgcn_s_memrealtime();
     }
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == kScanMin) {
         const uint32_t wave = tid >> 6;
         if ((tid & 63u) == 0) { sh_best[wave][0] = wb.h; sh_best[wave][1] = wb.n; }
         __syncthreads();
@@ -1139,13 +1136,13 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(const LaunchDesc
             }
         }
     }
-    if constexpr (MODE == 4) {  // leave the last job
+    if constexpr (MODE == kScanBatch) {  // leave the last job
         const uint32_t cur = __builtin_amdgcn_readfirstlane(batch_state().job);
         if (cur != kNoJob) batch_flush(wb, cur, sh_best);
     }
-    if constexpr (MODE == 5)  // leave the last job
+    if constexpr (MODE == kScanFirstBatch)  // leave the last job
         first_batch_flush(__builtin_amdgcn_readfirstlane(batch_state().job));
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == kScanFirst) {
         // the workgroup's lowest-nonce hit, appended only if it has one (the host reads
         // "found" off the append counter).  The pair is stored SWAPPED, nonce in .hash, so
         // k_reduce's lexicographic minimum picks the lowest nonce.

@@ -12,6 +12,7 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import pytest
 
@@ -125,6 +126,34 @@ def test_kernel_source_has_no_tuning_hooks():
         assert "GPUHASH_" + hook not in src
     patch = open(os.path.join(ROOT, "tools", "tuning_hooks.patch")).read()
     assert all("GPUHASH_" + h in patch for h in ("SALU_SIGMA", "FOLD_PLAIN", "EXTRA_SALU", "LT_ALIGN"))
+
+
+def test_every_kernel_is_the_recorded_one():
+    """Every kernel of every product object against tests/golden/kernel_manifest.txt: the
+    SHA-256 of its code bytes, its register and segment figures and its metadata entry
+    (tools/kernel_manifest.py).  A refactor of the kernel sources or of their build keeps them
+    all; a change meant to alter a kernel alters exactly the lines it means to.
+    After an intended kernel change or a compiler update, regenerate the fixture:
+    make -C bitcoin-miner_amd && python tools/kernel_manifest.py > tests/golden/kernel_manifest.txt"""
+    if not (shutil.which("objcopy") and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
+        pytest.skip("binutils / ROCm LLVM tools not present")
+    golden = {}
+    for line in open(os.path.join(ROOT, "tests", "golden", "kernel_manifest.txt")).read().splitlines():
+        obj, sym, rest = line.split(" ", 2)
+        golden[obj, sym] = rest
+    objs = sorted({obj for obj, _ in golden})
+    missing = [f"build/{o}" for o in objs if not os.path.exists(os.path.join(PKG, "build", o))]
+    if missing:
+        subprocess.check_call(["make", "-s", "-j8", "-C", PKG] + missing)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "kernel_manifest.py")]
+                                  + [os.path.join(PKG, "build", o) for o in objs], text=True)
+    built = {}
+    for line in out.splitlines():
+        obj, sym, rest = line.split(" ", 2)
+        built[obj, sym] = rest
+    assert len(golden) == 129 and sorted(built) == sorted(golden), sorted(set(built) ^ set(golden))
+    differ = [f"{obj} {sym}" for (obj, sym), rest in sorted(golden.items()) if built[obj, sym] != rest]
+    assert not differ, f"{len(differ)} kernels differ from the fixture:\n" + "\n".join(differ)
 
 
 def test_config2_kernel_code_is_the_measured_one(tmp_path):
