@@ -113,4 +113,62 @@ private:
     Split split_;
 };
 
+// ---- gpuhash_collect_below_batch: from one run of a batch to every job's exact answer ----
+//
+// What one run of n jobs gives (the scan kernel's MODE 6, scan_kernel.h): counts[k], job k's
+// exact hit counter, whatever the list holds; and the first min(appended, B) entries of the ONE
+// list the listing jobs share, each {hash, nonce, job}, in the order the waves appended them.
+// A job that does not list (cap_k == 0) appends nothing.  For a job that lists, every hit was
+// counted once and either stored once or not at all (its slot lay past the list's end), so with
+// listed_k the number of entries tagged k:
+//   total_k  is counts[k], always.  A re-run's count is never added: it recounts the same nonces.
+//   list     listed_k == counts[k]: the list holds ALL of job k's hits; sorted by nonce, the
+//            first cap_k are the lowest ones.  Otherwise the list filled up before job k was
+//            complete, and what it holds of job k is merely some of its hits: they are dropped
+//            and rerun(k, cap_k, out) runs job k alone, through the Collector above, which leaves
+//            in out its own total and the lowest min(cap_k, total) hits.  That total must equal
+//            counts[k] (both are exact counts of one range): anything else is `corrupt_rc`.
+// Jobs are independent, so the order of the re-runs does not matter; they run after the batch.
+struct JobHits {
+    uint64_t total = 0;
+    std::vector<Hit> held;  // the lowest min(cap, total) hits, ascending by nonce
+};
+
+// out[0..n): the jobs' answers.  *reruns, if given, counts the jobs that were re-run.
+// rerun(k, cap, JobHits&) -> 0 or an error code, which ends the fold.
+template <class Entry, class Rerun>
+int fold_collect_batch(size_t n, const uint64_t* counts, const Entry* list, size_t nlist, const size_t* caps,
+                       int corrupt_rc, Rerun&& rerun, JobHits* out, uint64_t* reruns = nullptr) {
+    std::vector<size_t> at(n + 1, 0);  // entries tagged k: sorted[at[k] .. at[k + 1])
+    for (size_t i = 0; i < nlist; i++) {
+        if (list[i].job >= n) return corrupt_rc;
+        at[(size_t)list[i].job + 1]++;
+    }
+    for (size_t k = 0; k < n; k++) at[k + 1] += at[k];
+    std::vector<Hit> sorted(nlist);
+    {
+        std::vector<size_t> next(at.begin(), at.end() - 1);
+        for (size_t i = 0; i < nlist; i++) sorted[next[list[i].job]++] = Hit{list[i].hash, list[i].nonce};
+    }
+    for (size_t k = 0; k < n; k++) {
+        out[k].total = counts[k];
+        out[k].held.clear();
+        if (!caps[k]) continue;
+        const size_t listed = at[k + 1] - at[k];
+        if (listed == counts[k]) {
+            const auto b = sorted.begin() + (std::ptrdiff_t)at[k], e = sorted.begin() + (std::ptrdiff_t)at[k + 1];
+            std::sort(b, e, [](const Hit& x, const Hit& y) { return x.nonce < y.nonce; });
+            out[k].held.assign(b, b + (std::ptrdiff_t)std::min(listed, caps[k]));
+            continue;
+        }
+        if (listed > counts[k]) return corrupt_rc;  // more stored than counted
+        JobHits again;
+        if (reruns) ++*reruns;
+        if (int rc = rerun(k, caps[k], again)) return rc;
+        if (again.total != counts[k]) return corrupt_rc;
+        out[k].held = std::move(again.held);
+    }
+    return 0;
+}
+
 }  // namespace gpuhash

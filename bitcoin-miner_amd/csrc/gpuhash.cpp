@@ -72,6 +72,13 @@ struct Dev {
     std::vector<BatchEntry> bat_list;
     std::vector<uint64_t> bat_h, bat_n;
     std::vector<uint8_t> bat_found;  // first-hit batch: the job has an entry
+    // collect batch: the ONE list its listing jobs share (GPUHASH_COLLECT_MAX BatchEntry, 24 MB,
+    // unless GPUHASH_COLLECT_BUFFER says otherwise), allocated on the entry's first batch with a
+    // listing job, grow-only; and the jobs' exact hit counters as they came back (bat_list then
+    // holds the first min(appended, capacity) entries of the list)
+    BatchEntry* d_blist = nullptr;
+    size_t blist_cap = 0;
+    std::vector<uint64_t> bat_counts;
     bool used = false;
     double kernel_ms = 0;
     uint32_t launches = 0;
@@ -205,6 +212,7 @@ static void dev_free(Dev& d) {
     if (d.d_best) hipFree(d.d_best);
     if (d.d_cands) hipFree(d.d_cands);
     if (d.d_hits) hipFree(d.d_hits);
+    if (d.d_blist) hipFree(d.d_blist);
     if (d.h_best) hipHostFree(d.h_best);
     if (d.h_nhit) hipHostFree(d.h_nhit);
     if (d.d_meta) hipFree(d.d_meta);
@@ -265,6 +273,13 @@ struct ModeWiring {
     // holds real hits only and is folded per job by the LOWEST NONCE; a job without an entry has
     // no hit.
     bool batch_first;
+    // A batch whose per-job words are triples, {the job's exact hit counter, armed to 0; its
+    // target; whether it lists}, in a job-major stage (stage.h, Stage::collects).  cands is the
+    // entry's d_blist, one list for all listing jobs, and the head's append counter is 64 bits
+    // wide: it comes back in h_best->hash.  After the wait the per-job words and the first
+    // min(appended, capacity) entries are copied; collect.h's fold_collect_batch makes every
+    // job's answer of them.
+    bool batch_collect;
 };
 constexpr ModeWiring kWiring[] = {
     /* kScanMin     */ {false, false, false, true},
@@ -273,6 +288,7 @@ constexpr ModeWiring kWiring[] = {
     /* kScanCollect */ {true, true, false, false},
     /* kScanBatch   */ {false, false, false, false, true},
     /* kScanFirstBatch */ {false, false, false, false, true, true},
+    /* kScanCollectBatch */ {false, false, false, false, true, false, true},
 };
 
 // dev_run, phase 1: reserves the entry's buffers, writes and uploads the launch metadata in one
@@ -297,6 +313,8 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
         (rc = grow(d.d_ktab, d.ktab_cap, st.tab_words)) || (rc = grow(d.d_hits, d.hits_cap, job.collect_cap)) ||
         (rc = grow(d.h_clk, d.clk_cap, kCounterBytes / 8 * std::max<size_t>(ng, 8), true)))
         return rc;
+    if (st.collects && std::any_of(st.lists.begin(), st.lists.end(), [](uint8_t l) { return l != 0; }))
+        if ((rc = grow(d.d_blist, d.blist_cap, st.list_cap))) return rc;
     while (d.ev.size() < 2 * ng) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
@@ -351,6 +369,7 @@ static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t 
             a.thresh = reinterpret_cast<unsigned long long*>(d.d_meta + st.thresh_at);
             a.cands = reinterpret_cast<Cand*>(d.d_meta + st.list_at + kBatchListHead);
             a.ncand = reinterpret_cast<unsigned int*>(d.d_meta + st.list_at);
+            if (w.batch_collect) a.cands = reinterpret_cast<Cand*>(d.d_blist);  // null: no job lists
         }
         a.dump = job.d_dump;
         a.dump_lo = w.takes_target ? job.target : lo;
@@ -368,7 +387,9 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
     const ModeWiring w = kWiring[job.mode];
     if (w.first_hit)
         HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_ncand, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
-    if (w.batch)
+    if (w.batch_collect)  // the 64-bit append counter, into the pinned h_best->hash
+        HIPCHK(hipMemcpyAsync(d.h_best, d.d_meta + st.list_at, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.stream));
+    else if (w.batch)
         HIPCHK(hipMemcpyAsync(d.h_nhit, d.d_meta + st.list_at, sizeof(unsigned int), hipMemcpyDeviceToHost, d.stream));
     if (w.reduces) HIPCHK(launch_reduce(d.d_cands, d.d_ncand, d.d_best, d.stream));
     // d_best, or the hit counter alone, which lands in the pinned h_best->hash
@@ -394,6 +415,21 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
 
 // dev_run, phase 4: the entry's results from what came back.
 static int decode(Dev& d, const ScanJob& job, const Stage& st) {
+    if (kWiring[job.mode].batch_collect) {
+        // the entries past the list's end were counted, not stored; a run without a listing job
+        // has no list at all (and appended nothing)
+        const size_t n = d.d_blist ? (size_t)std::min<uint64_t>(d.h_best->hash, st.list_cap) : 0;
+        std::vector<uint64_t> words(kCollectJobWords * st.njobs);
+        d.bat_list.resize(n);
+        if (n)
+            HIPCHK(hipMemcpyAsync(d.bat_list.data(), d.d_blist, n * sizeof(BatchEntry), hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(hipMemcpyAsync(words.data(), d.d_meta + st.thresh_at, words.size() * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, d.stream));
+        HIPCHK(hipStreamSynchronize(d.stream));
+        d.bat_counts.resize(st.njobs);
+        for (size_t k = 0; k < st.njobs; k++) d.bat_counts[k] = words[kCollectJobWords * k];
+        return GPUHASH_OK;
+    }
     if (kWiring[job.mode].batch) {
         const size_t n = *d.h_nhit;
         if (n > st.list_cap) return GPUHASH_EHIP;  // the bound is proved (stage.h): not reached
@@ -456,16 +492,21 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
 
 // Runs one entry's run of a sub-batch: the jobs [first, end) of `jobs`, whose plans are moved
 // into the stage; index0 is the batch index of jobs[0], for the launch records.
-// target: null for gpuhash_min_batch, else the targets of jobs[0..) for gpuhash_first_below_batch.
+// target: null for gpuhash_min_batch, else the targets of jobs[0..) for gpuhash_first_below_batch
+// and, with lists (whether each of jobs[0..) lists) and the entry's list capacity `buffer`, for
+// gpuhash_collect_below_batch.
 static int dev_run_batch(Dev& d, std::vector<PlannedJob>& jobs, size_t first, size_t end, size_t index0,
-                         uint32_t rchunk, const uint64_t* target = nullptr) {
+                         uint32_t rchunk, const uint64_t* target = nullptr, const uint8_t* lists = nullptr,
+                         uint64_t buffer = 0) {
     d.used = true;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(d.ord));
     std::vector<std::vector<Launch>> plans(end - first);
     for (size_t k = first; k < end; k++) plans[k - first] = std::move(jobs[k].plan);
-    const Stage st = target ? Stage(plans, target + first, rchunk) : Stage(plans, rchunk);
-    const ScanJob job{target ? kScanFirstBatch : kScanBatch};
+    const Stage st = lists    ? Stage(plans, target + first, lists + first, buffer, rchunk)
+                     : target ? Stage(plans, target + first, rchunk)
+                              : Stage(plans, rchunk);
+    const ScanJob job{lists ? kScanCollectBatch : target ? kScanFirstBatch : kScanBatch};
     std::vector<unsigned int> grids;
     int rc = stage_upload(d, st, job, grids);
     if (!rc) rc = arm_and_launch(d, st, job, 0, grids);
@@ -700,6 +741,13 @@ int gpuhash_first_below(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, ui
     return gpuhash_first_below_ex(ctx, msg, msg_len, lower, upper, target, 0, out_hash, out_nonce, out_found);
 }
 
+// The list capacity of collecting calls: GPUHASH_COLLECT_BUFFER overrides the device list's
+// entries (tests use it to reach the overflow paths on oracle-sized ranges).
+static uint32_t collect_buffer() {
+    const uint64_t env = env_u64("GPUHASH_COLLECT_BUFFER");
+    return env ? (uint32_t)std::min<uint64_t>(env, GPUHASH_COLLECT_MAX) : GPUHASH_COLLECT_MAX;
+}
+
 // gpuhash_collect_below_ex: search()'s slices and shards, with collect.h's collector between
 // the device runs and the outputs.  A slice's shards run concurrently, one per context entry;
 // a re-run of an overflowed sub-range runs alone, on its shard's entry.
@@ -708,10 +756,7 @@ static int collect(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
                    uint64_t* out_total) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     Call call(ctx);
-    // GPUHASH_COLLECT_BUFFER overrides the device list's entries (tests use it to reach
-    // the overflow path on oracle-sized ranges)
-    const uint64_t env = env_u64("GPUHASH_COLLECT_BUFFER");
-    const uint32_t buffer = env ? (uint32_t)std::min<uint64_t>(env, GPUHASH_COLLECT_MAX) : GPUHASH_COLLECT_MAX;
+    const uint32_t buffer = collect_buffer();
     auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
         split_slice(msg_len, lo, hi, (int)ctx->devs.size(), ctx->policy, batch);
     };
@@ -895,6 +940,143 @@ int gpuhash_first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_
                                         out_found);
 }
 
+// A re-run of one job of a collect batch: the job alone on context entry `shard`, through the
+// path gpuhash_collect_below takes (the Collector over [lo, hi], one shard, cap), which splits a
+// range that alone overflows the list.  Every launch record of it carries lo == hi == index.
+static int collect_alone(Call& call, int shard, size_t index, const uint8_t* msg, size_t msg_len, uint64_t lo,
+                         uint64_t hi, uint64_t target, uint32_t rchunk, uint32_t buffer, size_t cap, JobHits& out) {
+    gpuhash_ctx* const ctx = call.ctx;
+    const size_t recs0 = ctx->recs.size();
+    auto split = [&](uint64_t a, uint64_t b, std::vector<SubRange>& batch) { batch.push_back(SubRange{a, b, shard}); };
+    auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) -> int {
+        const ScanJob job{kScanCollect, target, want_list ? buffer : 0u};
+        if (int rc = call.run(msg, msg_len, rchunk, batch, job)) return rc;
+        for (size_t k = 0; k < batch.size(); k++) {
+            Dev& d = ctx->devs[(size_t)batch[k].shard];
+            res[k].count = d.hit_count;
+            res[k].hits = std::move(d.hits);
+            d.hits.clear();
+        }
+        return GPUHASH_OK;
+    };
+    Collector<decltype(run), decltype(split)> c(buffer, cap, run, split);
+    const int rc = c.collect(lo, hi, slice_width(1));
+    for (size_t i = recs0; i < ctx->recs.size(); i++) ctx->recs[i].lo = ctx->recs[i].hi = index;
+    out.total = c.total;
+    out.held = std::move(c.held);
+    return rc;
+}
+
+// gpuhash_collect_below_batch_ex, its arguments checked: min_batch's sub-batches and runs, each run
+// one collect batch stage (stage.h, Stage::collects) and one launch per group of it; then
+// collect.h's fold_collect_batch per run, whose re-runs follow the sub-batch on the run's entry.
+static int collect_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                               const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                               uint32_t rchunk, const size_t* out_off, uint64_t* out_nonces, uint64_t* out_hashes,
+                               uint64_t* out_totals) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Call call(ctx);
+    const uint32_t buffer = collect_buffer();
+    std::vector<JobHits> res(njobs);  // the outputs are written only when all ran
+    std::vector<size_t> caps(njobs, 0);
+    std::vector<uint8_t> lists(njobs, 0);
+    for (size_t k = 0; out_off && k < njobs; k++) {
+        caps[k] = out_off[k + 1] - out_off[k];
+        lists[k] = caps[k] ? 1 : 0;
+    }
+    const int policy = ctx->policy;
+    auto message = [&](size_t k, size_t& len) {
+        len = msg_off[k + 1] - msg_off[k];
+        return len ? msgs + msg_off[k] : nullptr;
+    };
+    auto plan = [&](size_t k) {
+        size_t len;
+        const uint8_t* const m = message(k, len);
+        return plan_job(BatchJob{m, len, lower[k], upper[k]}, rchunk, policy, /*host_ptab=*/false, /*pair=*/false,
+                        /*collects=*/true);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
+        const std::vector<std::pair<size_t, size_t>> runs = batch_runs(jobs, ctx->devs.size());
+        const int rc = call.run_each(runs.size(), [&](size_t r) {
+            Dev& d = ctx->devs[r];
+            d.rc = guarded([&] {
+                return dev_run_batch(d, jobs, runs[r].first, runs[r].second, first, rchunk, target + first,
+                                     lists.data() + first, buffer);
+            });
+        });
+        if (rc) return rc;
+        // a re-run resets every entry: take what the runs brought back first
+        std::vector<std::vector<BatchEntry>> list(runs.size());
+        std::vector<std::vector<uint64_t>> counts(runs.size());
+        for (size_t r = 0; r < runs.size(); r++) {
+            list[r] = std::move(ctx->devs[r].bat_list);
+            counts[r] = std::move(ctx->devs[r].bat_counts);
+            ctx->devs[r].bat_list.clear();
+            ctx->devs[r].bat_counts.clear();
+        }
+        for (size_t r = 0; r < runs.size(); r++) {
+            const size_t k0 = first + runs[r].first, n = runs[r].second - runs[r].first;
+            if (counts[r].size() != n) return GPUHASH_EHIP;
+            auto rerun = [&](size_t j, size_t cap, JobHits& out) {
+                const size_t k = k0 + j;
+                size_t len;
+                const uint8_t* const m = message(k, len);
+                return collect_alone(call, (int)r, k, m, len, lower[k], upper[k], target[k], rchunk, buffer, cap, out);
+            };
+            if (int frc = fold_collect_batch(n, counts[r].data(), list[r].data(), list[r].size(), caps.data() + k0,
+                                             GPUHASH_EHIP, rerun, res.data() + k0))
+                return frc;
+        }
+        return GPUHASH_OK;
+    };
+    if (int rc = for_each_sub_batch(njobs, batch_bytes_bound(), plan, run)) return rc;
+    uint64_t nonces = 0;  // every nonce is hashed: no early exit
+    for (size_t k = 0; k < njobs; k++) {
+        const uint64_t n = upper[k] - lower[k] + 1;  // <= GPUHASH_BATCH_MAX_SPAN
+        nonces = nonces + n < nonces ? ~0ull : nonces + n;
+    }
+    call.finish_nonces(nonces);
+    for (size_t k = 0; k < njobs; k++) {
+        out_totals[k] = res[k].total;
+        for (size_t i = 0; i < res[k].held.size(); i++) {
+            out_nonces[out_off[k] + i] = res[k].held[i].nonce;
+            out_hashes[out_off[k] + i] = res[k].held[i].hash;
+        }
+    }
+    return GPUHASH_OK;
+}
+
+int gpuhash_collect_below_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                   const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                   uint32_t rchunk, const size_t* out_off, uint64_t* out_nonces,
+                                   uint64_t* out_hashes, uint64_t* out_totals) {
+    if (!ctx || !msg_off || !lower || !upper || !target || !out_totals) return GPUHASH_EINVAL;
+    if (njobs == 0 || njobs > GPUHASH_BATCH_MAX_JOBS) return GPUHASH_EINVAL;
+    bool too_long = false;
+    for (size_t k = 0; k < njobs; k++) {
+        if (msg_off[k + 1] < msg_off[k] || lower[k] > upper[k]) return GPUHASH_EINVAL;
+        if (upper[k] - lower[k] >= GPUHASH_BATCH_MAX_SPAN) return GPUHASH_EINVAL;
+        if (out_off && (out_off[k + 1] < out_off[k] || out_off[k + 1] - out_off[k] > GPUHASH_COLLECT_MAX))
+            return GPUHASH_EINVAL;
+        too_long = too_long || msg_off[k + 1] - msg_off[k] > GPUHASH_MAX_MSG;
+    }
+    if (!msgs && msg_off[njobs] != msg_off[0]) return GPUHASH_EINVAL;
+    if (out_off && out_off[njobs] > 0 && (!out_nonces || !out_hashes)) return GPUHASH_EINVAL;
+    if (too_long) return GPUHASH_ETOOLONG;
+    return guarded([&] {
+        return collect_below_batch(ctx, msgs, msg_off, njobs, lower, upper, target, rchunk, out_off, out_nonces,
+                                   out_hashes, out_totals);
+    });
+}
+
+int gpuhash_collect_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                const size_t* out_off, uint64_t* out_nonces, uint64_t* out_hashes,
+                                uint64_t* out_totals) {
+    return gpuhash_collect_below_batch_ex(ctx, msgs, msg_off, njobs, lower, upper, target, 0, out_off, out_nonces,
+                                          out_hashes, out_totals);
+}
+
 int gpuhash_min(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t lower,
                 uint64_t upper, uint64_t* out_hash, uint64_t* out_nonce) {
     return gpuhash_min_ex(ctx, msg, msg_len, lower, upper, 0, out_hash, out_nonce);
@@ -964,9 +1146,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.7 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.8 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.7 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.8 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

@@ -21,6 +21,10 @@
  *   gpuhash_cli --batch-below FILE     -> lines "MSG LOWER UPPER TARGET"; prints per job, in order,
  *                                         "Result <hash> <nonce>" of the lowest nonce whose hash is
  *                                         <= TARGET, or "None", from ONE gpuhash_first_below_batch call
+ *   gpuhash_cli --batch-all-below FILE -> lines "MSG LOWER UPPER TARGET [CAP]"; prints per job, in order,
+ *                                         "Total <n>" and then one "Hit <hash> <nonce>" line for each
+ *                                         of the job's lowest CAP (default 256) nonces whose hash is
+ *                                         <= TARGET, ascending, from ONE gpuhash_collect_below_batch call
  *   gpuhash_cli --version
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
  */
@@ -46,8 +50,63 @@ static int fail(const char *what, int rc) {
     return 3;
 }
 
-/* --batch: every job of the file in one gpuhash_min_batch call; --batch-below (below != 0): in
- * one gpuhash_first_below_batch call, each line with a TARGET. */
+/* A --batch-all-below line without a CAP has room for this many hits: the output arrays hold the
+ * sum of the jobs' rooms, and the batch is built for sparse hits. */
+#define BATCH_ALL_DEFAULT_CAP 256
+
+/* --batch-all-below, the jobs read: one gpuhash_collect_below_batch call, --all-below's self-check
+ * per listed hit, and the output. */
+static int batch_all_main(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *off, size_t njobs, const uint64_t *lower,
+                          const uint64_t *upper, const uint64_t *target, const uint64_t *caps) {
+    size_t *out_off = (size_t *)malloc((njobs + 1) * sizeof *out_off);
+    uint64_t *totals = (uint64_t *)malloc(njobs * sizeof *totals);
+    uint64_t *nonces = NULL, *hashes = NULL;
+    int status = 0, oversized = 0;
+    if (out_off && totals) {
+        out_off[0] = 0;
+        for (size_t k = 0; k < njobs; k++) { /* an oversized CAP is the library's argument error to report */
+            oversized = oversized || caps[k] > GPUHASH_COLLECT_MAX;
+            out_off[k + 1] = out_off[k] + (caps[k] > GPUHASH_COLLECT_MAX ? (size_t)GPUHASH_COLLECT_MAX + 1 : (size_t)caps[k]);
+        }
+        /* ... which it does before it touches the arrays, so only then are they short */
+        const size_t room = oversized || !out_off[njobs] ? 1 : out_off[njobs];
+        nonces = (uint64_t *)malloc(room * sizeof *nonces);
+        hashes = (uint64_t *)malloc(room * sizeof *hashes);
+    }
+    if (!out_off || !totals || !nonces || !hashes) {
+        fprintf(stderr, "out of memory\n");
+        status = 3;
+    } else {
+        const int rc = gpuhash_collect_below_batch(ctx, msgs, off, njobs, lower, upper, target, out_off, nonces, hashes, totals);
+        if (rc) status = fail("gpuhash_collect_below_batch", rc);
+    }
+    for (size_t k = 0; k < njobs && !status; k++) {
+        const uint64_t held = totals[k] < caps[k] ? totals[k] : caps[k];
+        for (uint64_t i = 0; i < held && !status; i++) {
+            const uint64_t x = nonces[out_off[k] + i], h = hashes[out_off[k] + i];
+            if (gpuhash_hash_cpu(msgs + off[k], off[k + 1] - off[k], x) != h || h > target[k] || x < lower[k] ||
+                x > upper[k] || (i && x <= nonces[out_off[k] + i - 1])) {
+                fprintf(stderr, "self-check failed at job %zu, hit %" PRIu64 " (nonce %" PRIu64 ")\n", k, i, x);
+                status = 4;
+            }
+        }
+    }
+    for (size_t k = 0; k < njobs && !status; k++) {
+        const uint64_t held = totals[k] < caps[k] ? totals[k] : caps[k];
+        printf("Total %" PRIu64 "\n", totals[k]);
+        for (uint64_t i = 0; i < held; i++)
+            printf("Hit %" PRIu64 " %" PRIu64 "\n", hashes[out_off[k] + i], nonces[out_off[k] + i]);
+    }
+    free(out_off);
+    free(totals);
+    free(nonces);
+    free(hashes);
+    return status;
+}
+
+/* --batch: every job of the file in one gpuhash_min_batch call; --batch-below (below == 1): in
+ * one gpuhash_first_below_batch call, each line with a TARGET; --batch-all-below (below == 2): in
+ * one gpuhash_collect_below_batch call, each line with a TARGET and an optional CAP. */
 static int batch_main(const char *path, int below) {
     FILE *f = strcmp(path, "-") == 0 ? stdin : fopen(path, "r");
     if (!f) {
@@ -57,7 +116,7 @@ static int batch_main(const char *path, int below) {
     size_t njobs = 0, cap = 0, bytes = 0, bytes_cap = 0;
     uint8_t *msgs = NULL;
     size_t *off = NULL;
-    uint64_t *lower = NULL, *upper = NULL, *target = NULL;
+    uint64_t *lower = NULL, *upper = NULL, *target = NULL, *caps = NULL;
     char *line = NULL;
     size_t line_cap = 0;
     int status = 0;
@@ -67,10 +126,12 @@ static int batch_main(const char *path, int below) {
         if (!m) continue; /* an empty line */
         const char *lo = strtok_r(NULL, " \t\r\n", &save), *hi = strtok_r(NULL, " \t\r\n", &save);
         const char *tg = below ? strtok_r(NULL, " \t\r\n", &save) : NULL;
-        uint64_t a, b, t = 0;
-        if (!lo || !hi || (below && (!tg || parse_u64(tg, &t))) || strtok_r(NULL, " \t\r\n", &save) ||
-            parse_u64(lo, &a) || parse_u64(hi, &b)) {
-            fprintf(stderr, "line %zu: expected MSG LOWER UPPER%s\n", njobs + 1, below ? " TARGET" : "");
+        const char *cp = below == 2 ? strtok_r(NULL, " \t\r\n", &save) : NULL;
+        uint64_t a, b, t = 0, c = BATCH_ALL_DEFAULT_CAP;
+        if (!lo || !hi || (below && (!tg || parse_u64(tg, &t))) || (cp && parse_u64(cp, &c)) ||
+            strtok_r(NULL, " \t\r\n", &save) || parse_u64(lo, &a) || parse_u64(hi, &b)) {
+            fprintf(stderr, "line %zu: expected MSG LOWER UPPER%s\n", njobs + 1,
+                    below == 2 ? " TARGET [CAP]" : below ? " TARGET" : "");
             status = 2;
             break;
         }
@@ -81,12 +142,13 @@ static int batch_main(const char *path, int below) {
             lower = (uint64_t *)realloc(lower, cap * sizeof *lower);
             upper = (uint64_t *)realloc(upper, cap * sizeof *upper);
             target = (uint64_t *)realloc(target, cap * sizeof *target);
+            caps = (uint64_t *)realloc(caps, cap * sizeof *caps);
         }
         if (bytes + len + 1 > bytes_cap) {
             bytes_cap = 2 * (bytes + len + 1);
             msgs = (uint8_t *)realloc(msgs, bytes_cap);
         }
-        if (!off || !lower || !upper || !target || !msgs) {
+        if (!off || !lower || !upper || !target || !caps || !msgs) {
             fprintf(stderr, "out of memory\n");
             status = 3;
             break;
@@ -97,6 +159,7 @@ static int batch_main(const char *path, int below) {
         lower[njobs] = a;
         upper[njobs] = b;
         target[njobs] = t;
+        caps[njobs] = c;
         off[++njobs] = bytes;
     }
     free(line);
@@ -115,6 +178,9 @@ static int batch_main(const char *path, int below) {
         int rc = h && n && found ? gpuhash_open(NULL, 0, &ctx) : GPUHASH_ENOMEM;
         if (rc) {
             status = fail("gpuhash_open", rc);
+        } else if (below == 2) {
+            status = batch_all_main(ctx, msgs, off, njobs, lower, upper, target, caps);
+            gpuhash_close(ctx);
         } else if (below) {
             rc = gpuhash_first_below_batch(ctx, msgs, off, njobs, lower, upper, target, h, n, found);
             if (rc) status = fail("gpuhash_first_below_batch", rc);
@@ -149,6 +215,7 @@ static int batch_main(const char *path, int below) {
     free(n);
     free(found);
     free(target);
+    free(caps);
     free(msgs);
     free(off);
     free(lower);
@@ -163,12 +230,13 @@ int main(int argc, char **argv) {
     }
     if (argc == 3 && strcmp(argv[1], "--batch") == 0) return batch_main(argv[2], 0);
     if (argc == 3 && strcmp(argv[1], "--batch-below") == 0) return batch_main(argv[2], 1);
+    if (argc == 3 && strcmp(argv[1], "--batch-all-below") == 0) return batch_main(argv[2], 2);
     const int range_mode = argc == 5 && strcmp(argv[1], "--range") == 0;
     const int below_mode = argc == 6 && strcmp(argv[1], "--below") == 0;
     const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
     if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --batch-below FILE | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --batch-below FILE | --batch-all-below FILE | --version\n", argv[0]);
         return 2;
     }
     const int opt = range_mode || below_mode || all_mode;

@@ -239,6 +239,13 @@ struct Staged {
         read_groups();
     }
 
+    // A collect batch stage: as above, with lists[k] whether job k lists and the list's capacity.
+    Staged(std::vector<std::vector<Launch>>& plans, const uint64_t* target, const uint8_t* lists,
+           uint64_t buffer_entries, uint32_t rchunk)
+        : st(plans, target, lists, buffer_entries, rchunk), meta(st.bytes) {
+        read_groups();
+    }
+
    private:
     void read_groups() {
         st.fill(meta.data());
@@ -313,6 +320,28 @@ std::vector<size_t> piece_order(const VGroup& g, uint64_t order_seed, Rng& rng) 
     else if (order_seed != 0)
         for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[rng.next() % i]);
     return order;
+}
+
+// One run of the sub-range `sub` in collecting mode (the kernel's MODE 3): its groups back to back
+// on one counter and one list of `room` entries (0: count only); appends past the list's end are
+// counted and dropped.
+void collect_run(const uint8_t* msg, uint64_t len, const SubRange& sub, uint32_t rchunk, uint64_t target,
+                 int policy, uint64_t order_seed, Rng& rng, uint64_t room, SubResult& out) {
+    const Staged staged(msg, len, sub.lo, sub.hi, rchunk, policy);
+    for (const VGroup& g : staged.groups) {
+        std::vector<Part> parts;
+        for (size_t k : piece_order(g, order_seed, rng)) {
+            parts.clear();
+            cut_parts(g, g.pieces[k].first, g.pieces[k].second, parts);
+            for (const Part& pt : parts)
+                for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                    const uint64_t h = replay_hash(*pt.l, p, r);
+                    if (h > target) return;
+                    const uint64_t slot = out.count++;  // the atomic add
+                    if (slot < room) out.hits.push_back(Hit{h, n});
+                });
+        }
+    }
 }
 
 }  // namespace
@@ -428,22 +457,8 @@ int hostcheck_collect_below(const uint8_t* msg, uint64_t len, uint64_t lower, ui
     const uint64_t B = std::max<uint64_t>(buffer_entries, 1);
     auto run_one = [&](const SubRange& sub, bool want_list, SubResult& out) {
         runs++;
-        const uint64_t room = want_list ? B : 0;  // the word the kernel reads its capacity from
-        const Staged staged(msg, len, sub.lo, sub.hi, rchunk, policy);
-        for (const VGroup& g : staged.groups) {  // back to back, one counter and list
-            std::vector<Part> parts;
-            for (size_t k : piece_order(g, order_seed, rng)) {
-                parts.clear();
-                cut_parts(g, g.pieces[k].first, g.pieces[k].second, parts);
-                for (const Part& pt : parts)
-                    for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
-                        const uint64_t h = replay_hash(*pt.l, p, r);
-                        if (h > target) return;
-                        const uint64_t slot = out.count++;  // the atomic add
-                        if (slot < room) out.hits.push_back(Hit{h, n});
-                    });
-            }
-        }
+        // the word the kernel reads its capacity from
+        collect_run(msg, len, sub, rchunk, target, policy, order_seed, rng, want_list ? B : 0, out);
     };
     auto run = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& res) {
         for (size_t i = 0; i < batch.size(); i++) run_one(batch[i], want_list, res[i]);
@@ -971,6 +986,224 @@ int hostcheck_stage_first_batch(const uint8_t* msgs, const uint64_t* msg_off, ui
         plan_range(len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k], plans[k], rchunk, g_policy);
     }
     const Stage st(plans, target, rchunk);
+    for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
+        const StageGroup& g = st.groups[(size_t)i];
+        const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,
+                                  (uint64_t)g.c, g.total, g.nonces, g.work_at, g.offs_at, g.desc_at, g.ptab_at,
+                                  sizeof(LaunchDesc) * g.idx.size(), g.ptab_bytes};
+        std::memcpy(out + 14 * i, row, sizeof row);
+    }
+    *bytes = st.bytes;
+    const uint64_t ex[8] = {st.upload_bytes, st.thresh_at, st.job_words_bytes() * st.njobs, st.list_at, st.list_cap,
+                            sizeof(BatchEntry), st.tabs.size(), st.tab_words};
+    std::memcpy(extra, ex, sizeof ex);
+    if (meta && meta_cap >= st.bytes) {
+        std::memset(meta, 0, st.bytes);
+        st.fill(meta);
+    }
+    return (int)st.groups.size();
+}
+
+}  // extern "C"
+
+// ---- collect batch (gpuhash_collect_below_batch): CPU replay of the kernel's MODE 6 ----
+//
+// A collect batch stage's groups, pieces, parts and masks as k_scan<.., 6> walks them, from the
+// bytes fill() wrote: batch_find's lookup, the job change (nothing to flush: the workgroup takes
+// the new job's counter, target and list flag), the per-job counters and the ONE list with its
+// 64-bit append counter and its capacity.  What a GPU decides by timing -- which workgroup takes
+// which piece, and so the order of the appends and which hits a full list drops -- is chosen by a
+// seed, as in BatchReplay::group.  The host side is the engine's: collect.h's fold_collect_batch,
+// with the re-runs replayed as hostcheck_collect_below replays a single collection.
+
+namespace {
+
+struct CollectBatchReplay {
+    const Staged& run;
+    const uint64_t* words;  // per job: counter, target, lists -- as fill() armed them
+    std::vector<uint64_t> counts;
+    std::vector<BatchEntry> list;
+    uint64_t appended = 0;  // the list head's 64-bit counter
+    uint64_t cap;           // and its capacity
+    Rng* jitter = nullptr;
+
+    explicit CollectBatchReplay(const Staged& r)
+        : run(r), words(reinterpret_cast<const uint64_t*>(r.meta.data() + r.st.thresh_at)), counts(r.st.njobs) {
+        uint32_t head[4];
+        std::memcpy(head, r.meta.data() + r.st.list_at, sizeof head);
+        cap = head[2];
+        for (size_t k = 0; k < r.st.njobs; k++) counts[k] = words[kCollectJobWords * k];
+    }
+
+    void piece(const VGroup& g, ReplayWg& wg, uint64_t x, uint64_t end) {
+        while (x < end) {
+            if (jitter && jitter->next() % 4 == 0) wg.idx = (int)(jitter->next() % g.ls.size());
+            const int i = wg.idx = BatchReplay::find(g, wg.idx, x);
+            const LaunchDesc& D = g.descs[i];
+            const uint32_t rel = (uint32_t)(x - g.offs[i]);
+            const uint32_t row = rel / D.R, r0 = rel - row * D.R;
+            const uint64_t left = end - x;
+            const uint32_t r1 = (uint64_t)(D.R - r0) < left ? D.R : r0 + (uint32_t)left;
+            wg.job = D.job;  // the job change: no per-wave state to leave behind
+            const uint64_t target = words[kCollectJobWords * D.job + 1];
+            const bool lists = words[kCollectJobWords * D.job + 2] != 0;
+            const Part pt{g.ls[(size_t)i], &D, row, r0, r1, x, g.offs[i + 1]};
+            for_each_nonce(pt, [&](uint32_t p, uint32_t r, uint64_t n) {
+                const uint64_t h = replay_hash(*pt.l, p, r);
+                if (h > target) return;
+                counts[D.job]++;
+                if (!lists) return;
+                const uint64_t slot = appended++;
+                if (slot < cap) list.push_back(BatchEntry{h, n, D.job, 0});
+            });
+            x += r1 - r0;
+        }
+    }
+
+    // The workgroups and the order of their pieces: BatchReplay::group's three kinds.
+    void group(size_t gi, uint64_t order_seed, Rng& rng) {
+        const VGroup& g = run.groups[gi];
+        const size_t np = g.pieces.size();
+        jitter = order_seed > 1 ? &rng : nullptr;
+        const size_t grid = Stage::grid(run.st.groups[gi], std::min<unsigned int>(kReplayGrid, kBatchMaxGrid));
+        const size_t W = order_seed == 0 ? 1 : order_seed == 1 ? std::min(grid, np)
+                                                               : std::min({grid, np, (size_t)(2 + rng.next() % 7)});
+        std::vector<ReplayWg> wgs(W);
+        for (size_t k = 0; k < np; k++) {
+            const size_t w = order_seed == 0 ? 0 : order_seed == 1 ? k * W / np : rng.next() % W;
+            wgs[w].pieces.push_back(k);
+        }
+        auto step = [&](ReplayWg& wg) {
+            const auto& pc = g.pieces[wg.pieces[wg.next++]];
+            piece(g, wg, pc.first, pc.second);
+        };
+        if (order_seed <= 1) {
+            for (size_t w = W; w-- > 0;)
+                while (wgs[w].next < wgs[w].pieces.size()) step(wgs[w]);
+            return;
+        }
+        std::vector<size_t> live;
+        for (size_t w = 0; w < W; w++)
+            if (!wgs[w].pieces.empty()) live.push_back(w);
+        while (!live.empty()) {
+            const size_t at = rng.next() % live.size();
+            ReplayWg& wg = wgs[live[at]];
+            step(wg);
+            if (wg.next == wg.pieces.size()) live.erase(live.begin() + (long)at);
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// gpuhash_collect_below_batch as the engine runs it: the same sub-batches (for_each_sub_batch under
+// batch_bytes, 0: the engine's bound), runs over nshards context entries (batch_runs), collect
+// batch stages and fold (collect.h, fold_collect_batch), each run replayed as above with the order
+// of its pieces chosen by order_seed (0, 1 or a shuffle) and a list of buffer_entries entries, and
+// each re-run replayed as hostcheck_collect_below replays a collection (one shard, the same list
+// size).  msg_off has njobs + 1 entries; out_off has njobs + 1 entries or is null (every cap 0).
+// Returns 0 and out_totals[k], the lowest min(cap_k, total_k) hits of job k from out_off[k] on in
+// out_nonces / out_hashes (untouched beyond), and in out_info[0..3]: the largest number of entries
+// any run's list held, the number of jobs that were re-run, the number of sub-batches, and the
+// number of sub-range runs the re-runs' collectors asked for.
+int hostcheck_collect_below_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs,
+                                  const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                  uint32_t rchunk, int policy, uint64_t order_seed, uint64_t batch_bytes,
+                                  int nshards, uint64_t buffer_entries, const uint64_t* out_off,
+                                  uint64_t* out_nonces, uint64_t* out_hashes, uint64_t* out_totals,
+                                  uint64_t* out_info) {
+    if (!msg_off || !lower || !upper || !target || !out_totals || !out_info || !njobs || nshards < 1) return -1;
+    std::vector<size_t> caps(njobs, 0);
+    std::vector<uint8_t> lists(njobs, 0);
+    for (uint64_t k = 0; k < njobs; k++) {
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+        if (out_off && out_off[k + 1] < out_off[k]) return -1;
+        caps[k] = out_off ? (size_t)(out_off[k + 1] - out_off[k]) : 0;
+        lists[k] = caps[k] ? 1 : 0;
+    }
+    if (out_off && out_off[njobs] > 0 && (!out_nonces || !out_hashes)) return -1;
+    Rng rng{order_seed};
+    const uint64_t B = std::max<uint64_t>(buffer_entries, 1);
+    uint64_t info[4] = {0, 0, 0, 0};
+    std::vector<JobHits> res(njobs);
+    auto message = [&](size_t k, uint64_t& len) {
+        len = msg_off[k + 1] - msg_off[k];
+        return len ? msgs + msg_off[k] : nullptr;
+    };
+    auto plan = [&](size_t k) {
+        uint64_t len;
+        const uint8_t* const m = message(k, len);
+        return plan_job(BatchJob{m, len, lower[k], upper[k]}, rchunk, policy, /*host_ptab=*/true, /*pair=*/false,
+                        /*collects=*/true);
+    };
+    auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
+        info[2]++;
+        const auto runs = batch_runs(jobs, (size_t)nshards);
+        for (size_t ri = 0; ri < runs.size(); ri++) {
+            const auto& r = runs[ri];
+            const size_t k0 = first + r.first, n = r.second - r.first;
+            std::vector<std::vector<Launch>> plans(n);
+            for (size_t k = r.first; k < r.second; k++) plans[k - r.first] = std::move(jobs[k].plan);
+            const Staged staged(plans, target + k0, lists.data() + k0, B, rchunk);
+            CollectBatchReplay rep(staged);
+            for (size_t gi = 0; gi < staged.groups.size(); gi++) rep.group(gi, order_seed, rng);
+            info[0] = std::max<uint64_t>(info[0], rep.list.size());
+            auto rerun = [&](size_t j, size_t cap, JobHits& out) {
+                const size_t k = k0 + j;
+                uint64_t len;
+                const uint8_t* const m = message(k, len);
+                auto one = [&](const std::vector<SubRange>& batch, bool want_list, std::vector<SubResult>& rs) {
+                    for (size_t i = 0; i < batch.size(); i++) {
+                        info[3]++;
+                        collect_run(m, len, batch[i], rchunk, target[k], policy, order_seed, rng, want_list ? B : 0,
+                                    rs[i]);
+                    }
+                    return 0;
+                };
+                auto split = [&](uint64_t a, uint64_t b, std::vector<SubRange>& batch) {
+                    batch.push_back(SubRange{a, b, (int)ri});
+                };
+                Collector<decltype(one), decltype(split)> c(B, cap, one, split);
+                const int rc = c.collect(lower[k], upper[k], slice_width(1));
+                out.total = c.total;
+                out.held = std::move(c.held);
+                return rc;
+            };
+            if (int rc = fold_collect_batch(n, rep.counts.data(), rep.list.data(), rep.list.size(), caps.data() + k0,
+                                            -3, rerun, res.data() + k0, &info[1]))
+                return rc;
+        }
+        return 0;
+    };
+    if (int rc = for_each_sub_batch((size_t)njobs, batch_bytes_bound(batch_bytes), plan, run)) return rc;
+    for (uint64_t k = 0; k < njobs; k++) {
+        out_totals[k] = res[k].total;
+        for (size_t i = 0; i < res[k].held.size(); i++) {
+            out_nonces[out_off[k] + i] = res[k].held[i].nonce;
+            out_hashes[out_off[k] + i] = res[k].held[i].hash;
+        }
+    }
+    std::memcpy(out_info, info, sizeof info);
+    return 0;
+}
+
+// The stage of ONE run of a collect batch, as hostcheck_stage_batch gives a batch's: the same
+// words (the per-job region's size is then 24 bytes per job; the list's position is that of its
+// 16-byte head, which ends the buffer, and its capacity buffer_entries).
+int hostcheck_stage_collect_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs,
+                                  const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                  const uint8_t* lists, uint64_t buffer_entries, uint32_t rchunk, uint64_t* out,
+                                  int cap, uint64_t* bytes, uint64_t* extra, uint8_t* meta, uint64_t meta_cap) {
+    if (!msg_off || !lower || !upper || !target || !lists || !bytes || !extra || !njobs) return -1;
+    std::vector<std::vector<Launch>> plans(njobs);
+    for (uint64_t k = 0; k < njobs; k++) {
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        plan_range(len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k], plans[k], rchunk, g_policy);
+    }
+    const Stage st(plans, target, lists, buffer_entries, rchunk);
     for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
         const StageGroup& g = st.groups[(size_t)i];
         const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,

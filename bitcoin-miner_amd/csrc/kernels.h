@@ -26,7 +26,8 @@ struct ScanArgs {
     unsigned int gmin, gmax;         // piece size bounds (r values per grab; stage.h)
     unsigned long long* thresh;      // the shared 64-bit word: a bound or the hit counter
                                      // (batch: one pruning word per job; first-hit batch: a
-                                     // bound and a target per job)
+                                     // bound and a target per job; collect batch: a hit
+                                     // counter, a target and a list flag per job)
     Cand* cands;                     // appended candidates, or the hit list (batch: the result
                                      // list, BatchEntry)
     unsigned int* ncand;             // append counter, or the hit list's capacity
@@ -38,7 +39,8 @@ struct ScanArgs {
 
 // The scan kernels' MODE template parameter (scan_kernel.h), by name on the host.
 enum ScanMode : int {
-    kScanMin = 0, kScanDump = 1, kScanFirst = 2, kScanCollect = 3, kScanBatch = 4, kScanFirstBatch = 5
+    kScanMin = 0, kScanDump = 1, kScanFirst = 2, kScanCollect = 3, kScanBatch = 4, kScanFirstBatch = 5,
+    kScanCollectBatch = 6
 };
 
 // Resident workgroups of 256 threads for the (J, C2, EX, mode) kernel on this device.
@@ -48,7 +50,8 @@ unsigned int grid_for(int J, int C2, int EX, int mode, int device);
 // search, 1: per-nonce dump, 2: first hit at or below a target (gpuhash_first_below), 3: every
 // hit at or below a target, counted and listed (gpuhash_collect_below), 4: the argmin search of
 // every job of a batch (gpuhash_min_batch), 5: the first hit of every job of a batch
-// (gpuhash_first_below_batch).
+// (gpuhash_first_below_batch), 6: every hit of every job of a batch, counted per job and listed
+// (gpuhash_collect_below_batch).
 hipError_t launch_scan(int J, int C2, int EX, int mode, const ScanArgs& a);
 // Fills the uniform K+W table of a C2/J=0 descriptor: tab[64*r + t] = K[t] + W_t(r),
 // r in [0, D.R), for block B's words U with the loop digits of r inserted into W_0.

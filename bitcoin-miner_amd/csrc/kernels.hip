@@ -132,6 +132,7 @@ static auto with_mode(int J, int C2, int EX, int mode, F&& f) {
         case kScanCollect: return with_variant<kScanCollect>(J, C2, EX, f);
         case kScanBatch: return with_variant<kScanBatch>(J, C2, EX, f);
         case kScanFirstBatch: return with_variant<kScanFirstBatch>(J, C2, EX, f);
+        case kScanCollectBatch: return with_variant<kScanCollectBatch>(J, C2, EX, f);
         default: return with_variant<kScanDump>(J, C2, EX, f);
     }
 }

@@ -95,6 +95,10 @@ struct BatchEntry {
     uint32_t job, pad_;
 };
 
+// 64-bit words per job in the per-job region of a collect batch stage (gpuhash_collect_below_batch;
+// stage.h, Stage::collects): the job's hit counter, its target, whether it lists.
+constexpr uint32_t kCollectJobWords = 3;
+
 #ifdef __HIPCC__
 #define GPUHASH_HD __host__ __device__
 #else

@@ -4,7 +4,7 @@
 // (tools/variant_bench.py).
 // A family source states its layouts once and is compiled once per mode group, into a code
 // object each (Makefile, MODE_GROUPS): MODE 0 and 1 of every layout without GPUHASH_MODE, MODE N
-// alone with -DGPUHASH_MODE=N (2..5).  kernels.hip launches the kernels through these
+// alone with -DGPUHASH_MODE=N (2..6).  kernels.hip launches the kernels through these
 // declarations only, so nothing is implicitly instantiated there.
 #pragma once
 #include <stdint.h>

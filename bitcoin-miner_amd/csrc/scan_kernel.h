@@ -39,6 +39,10 @@
 // MODE 2's per-nonce test, slow path, skip and drain rules against the CURRENT JOB's bound and
 // target, and MODE 4's descriptor lookup, job change and result list (first_batch_flush, below).
 //
+// MODE 6 (kScanCollectBatch) is MODE 3 for a batch of independent jobs, gpuhash_collect_below_batch:
+// MODE 3's per-nonce test and append path against the CURRENT JOB's target and counter, and MODE
+// 4's descriptor lookup and job change (CollectBatchState, below).
+//
 // Every mode group is a code object of its own (scan_decl.h), and each mode compiles to the same
 // machine code whatever the others hold: tests/golden/kernel_manifest.txt pins every kernel.
 #pragma once
@@ -73,7 +77,9 @@ namespace gpuhash {
 // MODE is a ScanMode (kernels.h).  The first-hit modes share the per-nonce test and the skip
 // rule, the batch modes the descriptor lookup and the result list.
 constexpr bool is_first_mode(int mode) { return mode == kScanFirst || mode == kScanFirstBatch; }
-constexpr bool is_batch_mode(int mode) { return mode == kScanBatch || mode == kScanFirstBatch; }
+constexpr bool is_batch_mode(int mode) {
+    return mode == kScanBatch || mode == kScanFirstBatch || mode == kScanCollectBatch;
+}
 
 namespace dev {
 
@@ -471,6 +477,74 @@ __device__ __forceinline__ int batch_find(const unsigned long long* __restrict__
     return i;
 }
 
+// MODE 6 (collect batch, gpuhash_collect_below_batch): MODE 3's question for many independent jobs
+// in one launch per kernel variant, in MODE 4's job-major stage.  k_scan's arguments are MODE 4's,
+// except:
+//   thresh   THREE 64-bit words per job (kCollectJobWords): thresh[3 * job] is the job's exact hit
+//            counter (armed to 0), thresh[3 * job + 1] its target, thresh[3 * job + 2] whether the
+//            job lists at all (cap_k > 0), both READ-ONLY here
+//   cands    the ONE list all listing jobs share, BatchEntry{hash, nonce, job}
+//   ncand    the list's head: a 64-bit append counter (armed to 0), then its capacity (a uint32)
+// Per nonce nothing differs from MODE 3 (wb.T is the high word of the current job's target).  The
+// slow path adds the ballot's popcount to the JOB's counter, and, if the job lists, reserves that
+// many slots with one atomic add on the list's append counter and stores its hits at them, tagged
+// with the job, each only while its slot is below the capacity.  The append counter is 64 bits
+// wide and slots are compared as 64-bit: a run's hits are bounded only by its nonces (2^16 jobs of
+// 2^38), so a 32-bit counter could wrap back into the list.  A job's counter is exact whatever the
+// list holds; each hit is stored once or not at all, so a job whose tagged entries number its
+// counter has all its hits in the list, and the host re-runs alone a job that has not.
+// No per-wave state belongs to a job: at a job change (MODE 4's place: between rows, all four waves
+// at the barriers) nothing is flushed, thread 0 publishes the new job's counter address, target
+// and list flag through LDS between two barriers, and every wave re-arms wb.T.  Nothing happens at
+// the end of the kernel; no workgroup waits on another.
+// As in MODE 3 the words live in LDS and come back to scalar registers on the slow path only, so
+// nothing new is live across the per-nonce loop.  The stores are lane 0's ordinary vector stores
+// of wave-uniform values.
+struct CollectBatchState {
+    unsigned long long* count;  // the current job's hit counter
+    uint32_t target_hi, target_lo;
+    uint32_t cap;  // the list's capacity in entries if the current job lists, else 0
+};
+__device__ __forceinline__ CollectBatchState& collect_batch_state() {
+    __shared__ CollectBatchState cbs;
+    return cbs;
+}
+
+// collect_ballot for the current job's target.
+__device__ __forceinline__ unsigned long long collect_batch_ballot(uint32_t H0, uint32_t H1, uint32_t T, bool ok) {
+    const uint32_t tlo = __builtin_amdgcn_readfirstlane(collect_batch_state().target_lo);
+    return __builtin_amdgcn_ballot_w64(ok && (H0 < T || (H0 == T && H1 <= tlo)));
+}
+
+// Counts the hits of ballot m (non-empty) for the current job and returns the list slot of its
+// first one; a job that does not list reserves nothing and gets a slot no capacity is above.
+__device__ __forceinline__ unsigned long long collect_batch_reserve(unsigned long long m) {
+    unsigned long long slot = ~0ull;
+    if ((threadIdx.x & 63u) == 0) {
+        const CollectBatchState& cbs = collect_batch_state();
+        const unsigned long long n = (unsigned long long)__builtin_popcountll(m);
+        atomicAdd(cbs.count, n);
+        if (cbs.cap) slot = atomicAdd(reinterpret_cast<unsigned long long*>(batch_state().count), n);
+    }
+    return uniform64(slot);
+}
+
+__device__ __forceinline__ bool collect_batch_room(unsigned long long slot) {
+    return slot < (unsigned long long)__builtin_amdgcn_readfirstlane(collect_batch_state().cap);
+}
+
+// slot < capacity (collect_batch_room); hh, nn wave-uniform.
+__device__ __forceinline__ void collect_batch_store(unsigned long long slot, unsigned long long hh,
+                                                    unsigned long long nn) {
+    if ((threadIdx.x & 63u) == 0) {
+        const BatchState& bs = batch_state();
+        BatchEntry* const e = bs.list + slot;
+        e->hash = hh;
+        e->nonce = nn;
+        e->job = bs.job;
+    }
+}
+
 // Rounds 0..63 of block B when its whole message schedule is wave-uniform (C2 layouts
 // whose loop digits are the only digits in block B): kw[t] = K[t] + W_t comes from a
 // table, the per-lane input is the state s after block B-1 (= cv), so a nonce costs 64
@@ -635,6 +709,26 @@ __device__ __forceinline__ void scan_row(const LaunchDesc& D, uint32_t row, uint
                         const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
                         const unsigned long long nn = (D.base + (unsigned long long)pl * D.R + r) * D.stride + D.tail;
                         collect_store(slot++, hh, nn);
+                    }
+                }
+            }
+        } else if constexpr (MODE == kScanCollectBatch) {
+            // collect batch: MODE 3's walk, against the current job's target, counter and list flag
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {
+                const bool ok = lane_ok && r >= rlo && r <= rhi;
+                m = collect_batch_ballot(H0, H1, wb.T, ok);
+                if (m) {
+                    unsigned long long slot = collect_batch_reserve(m);
+                    while (m && collect_batch_room(slot)) {
+                        const int l = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                        const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                        const uint32_t pl = __builtin_amdgcn_readlane(p, l);
+                        const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                        const unsigned long long nn = (D.base + (unsigned long long)pl * D.R + r) * D.stride + D.tail;
+                        collect_batch_store(slot++, hh, nn);
                     }
                 }
             }
@@ -839,6 +933,24 @@ __device__ __forceinline__ void scan_row_lt(const LaunchDesc& D, uint32_t row, u
                     }
                 }
             }
+        } else if constexpr (MODE == kScanCollectBatch) {
+            unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
+            if (m) {  // collect batch: as scan_row's MODE 6
+                m = collect_batch_ballot(H0, H1, wb.T, lane_ok);
+                if (m) {
+                    unsigned long long slot = collect_batch_reserve(m);
+                    while (m && collect_batch_room(slot)) {
+                        const int l = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const uint32_t h0 = __builtin_amdgcn_readlane(H0, l);
+                        const uint32_t h1 = __builtin_amdgcn_readlane(H1, l);
+                        const uint32_t xl = __builtin_amdgcn_readlane(x, l);
+                        const unsigned long long hh = ((unsigned long long)h0 << 32) | h1;
+                        const unsigned long long nn = D.base + (unsigned long long)r * D.RQ + xl;
+                        collect_batch_store(slot++, hh, nn);
+                    }
+                }
+            }
         } else {
             unsigned long long m = __builtin_amdgcn_ballot_w64(H0 <= wb.T);
             if (m) {  // wave-uniform, rare once T has settled
@@ -947,6 +1059,10 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(GPUHASH_SCAN_PAR
         if ((tid & 63u) == 0) fs.found[tid >> 6] = 0u;
         __syncthreads();
     }
+    if constexpr (MODE == kScanCollectBatch) {  // thresh, cands, ncand: see CollectBatchState
+        if (tid == 0) batch_arm(thresh, cands, ncand);  // no job yet: the first part changes to one
+        __syncthreads();
+    }
     for (;;) {
         // MODE 5 keeps the bound of the grab in LDS alone (grab_bound) and every wave reads it
         // back at each part: no wave may still be among the parts of the last piece when thread 0
@@ -975,7 +1091,9 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(GPUHASH_SCAN_PAR
         if constexpr (MODE == kScanFirst) grab_bound = uniform64(first_state().grab_bound);
         __syncthreads();
         unsigned long long end;
-        if constexpr (MODE == kScanFirstBatch) {  // the same two tests, on the scalar unit
+        // the same two tests, on the scalar unit (MODE 6 as well: the VGPR copy of `total` that
+        // the 64-bit compares keep went to scratch at J = 7, 8, 12 and 13)
+        if constexpr (MODE == kScanFirstBatch || MODE == kScanCollectBatch) {
             if (!uniform_lt64(x, total)) break;
             end = uniform_lt64(x + g, total) ? x + g : total;
         } else {
@@ -1062,6 +1180,29 @@ __global__ __launch_bounds__(256) GPUHASH_SCAN_ATTR void k_scan(GPUHASH_SCAN_PAR
                     }
                     __syncthreads();
                     wb.T = __builtin_amdgcn_readfirstlane((uint32_t)(fs.target >> 32));
+                }
+            }
+            if constexpr (MODE == kScanCollectBatch) {
+                // a part of another job: nothing to flush (no per-wave state belongs to a job).
+                // Thread 0 publishes the new job's counter address, target and list flag between
+                // the barriers: every wave has left the old job before, and reads the new words after.
+                BatchState& bs = batch_state();
+                const uint32_t job = __builtin_amdgcn_readfirstlane(D.job);
+                const uint32_t cur = __builtin_amdgcn_readfirstlane(bs.job);
+                if (job != cur) {
+                    __syncthreads();
+                    CollectBatchState& cbs = collect_batch_state();
+                    if (tid == 0) {
+                        unsigned long long* const words = bs.thresh + (unsigned long long)kCollectJobWords * job;
+                        const unsigned long long target = words[1];
+                        bs.job = job;
+                        cbs.count = words;
+                        cbs.target_hi = (uint32_t)(target >> 32);
+                        cbs.target_lo = (uint32_t)target;
+                        cbs.cap = words[2] ? bs.count[2] : 0u;
+                    }
+                    __syncthreads();
+                    wb.T = __builtin_amdgcn_readfirstlane(cbs.target_hi);
                 }
             }
             const uint32_t row = rel / D.R, r0 = rel - row * D.R;

@@ -109,12 +109,16 @@ inline uint64_t batch_job_entries(uint64_t span, uint32_t gmin, uint64_t grid) {
 // A first-hit batch (pair) has two words per job, and may put every launch in a group of its own:
 // the group's second prefix offset then takes 8 of the 64 bytes priced for the gaps, which are
 // at most 15 wide there (the offsets and the descriptors end 16-byte aligned).
-inline uint64_t batch_job_bytes(const std::vector<Launch>& plan, uint32_t gmin, bool pair = false) {
-    uint64_t b = (pair ? 16 : 8) + 16;  // its pruning word (pair: bound and target); its share of the list head
+// A collect batch (collects) has three words per job and no list in the buffer: its list is the
+// entry's fixed device buffer (Stage::collects), which the bound does not count.
+inline uint64_t batch_job_bytes(const std::vector<Launch>& plan, uint32_t gmin, bool pair = false,
+                                bool collects = false) {
+    // its pruning word (pair: bound and target; collects: counter, target, list flag); its share of the list head
+    uint64_t b = (collects ? 24 : pair ? 16 : 8) + 16;
     for (const Launch& l : plan) {
         b += sizeof(LaunchDesc) + 8 + kCounterBytes + 4 * 16;
         b += sizeof(uint32_t) * l.nptab;
-        b += sizeof(BatchEntry) * batch_job_entries(row_iterations(l.desc), gmin, kBatchMaxGrid);
+        if (!collects) b += sizeof(BatchEntry) * batch_job_entries(row_iterations(l.desc), gmin, kBatchMaxGrid);
     }
     return b;
 }
@@ -151,11 +155,11 @@ struct PlannedJob {
 };
 
 inline PlannedJob plan_job(const BatchJob& j, uint32_t rchunk, int policy, bool host_ptab = false,
-                           bool pair = false) {
+                           bool pair = false, bool collects = false) {
     PlannedJob p;
     plan_range(j.msg, j.len, j.lo, j.hi, p.plan, rchunk, policy, host_ptab);
     const uint32_t gmax = rchunk ? rchunk : kDefaultMaxPiece;
-    p.bytes = batch_job_bytes(p.plan, std::min(kMinPiece, gmax), pair);
+    p.bytes = batch_job_bytes(p.plan, std::min(kMinPiece, gmax), pair, collects);
     p.cost = plan_cost(p.plan);
     return p;
 }
@@ -241,7 +245,18 @@ struct Stage {
     // job: the bound, the lowest qualifying nonce found so far (armed to all ones), then the job's
     // target.  The result list is a batch stage's.
     bool by_digits = false;
-    std::vector<uint64_t> targets;  // by_digits: one per job
+    std::vector<uint64_t> targets;  // by_digits, collects: one per job
+    // A collect batch stage (gpuhash_collect_below_batch; collects): a batch stage in the job-major
+    // order of the min_batch constructor (there is no early exit for an order to protect).  The
+    // per-job region at thresh_at holds THREE 64-bit words per job: the job's exact hit counter
+    // (armed to 0), its target, and whether the job lists at all (cap_k > 0).  The buffer ends with
+    // the list's head at list_at: a 64-bit append counter (armed to 0), the capacity list_cap as a
+    // uint32, padding.  The list itself is NOT in the buffer: it is the entry's own device array of
+    // list_cap = buffer_entries BatchEntry, shared by all listing jobs.  That capacity is not a
+    // proved bound (it depends on the hits): the host finds the jobs it cut short by their
+    // counters and re-runs them (collect.h, fold_collect_batch).
+    bool collects = false;
+    std::vector<uint8_t> lists;  // collects: one per job, cap_k > 0
 
     Stage(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy,
           bool host_ptab = false) : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)) {
@@ -274,10 +289,25 @@ struct Stage {
         lay_out();
     }
 
+    // The stage of a collect batch: plans[k] as above, target[k] job k's target, lists[k] whether
+    // it lists, buffer_entries the capacity of the entry's list.  See collects.
+    Stage(std::vector<std::vector<Launch>>& plans, const uint64_t* target, const uint8_t* lists_,
+          uint64_t buffer_entries, uint32_t rchunk)
+        : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()),
+          list_cap((size_t)std::min<uint64_t>(buffer_entries, 0xFFFFFFFFull)),
+          targets(target, target + plans.size()), collects(true), lists(lists_, lists_ + plans.size()) {
+        for (size_t k = 0; k < plans.size(); k++)
+            for (Launch& l : plans[k]) {
+                l.desc.job = (uint32_t)k;
+                plan.push_back(std::move(l));
+            }
+        lay_out();
+    }
+
     static size_t aligned(size_t b) { return (b + 15) & ~(size_t)15; }
 
     // Bytes of a job's words in the per-job region.
-    size_t job_words_bytes() const { return by_digits ? 16 : 8; }
+    size_t job_words_bytes() const { return collects ? 24 : by_digits ? 16 : 8; }
 
    private:
     void lay_out() {
@@ -347,6 +377,11 @@ struct Stage {
         align();
         list_at = bytes;
         upload_bytes = list_at + kBatchListHead;
+        if (collects) {  // the list is the entry's own array: the buffer ends with its head
+            bytes = upload_bytes;
+            align();
+            return;
+        }
         for (const StageGroup& g : groups) {
             const uint64_t grid = Stage::grid(g, kBatchMaxGrid);
             uint64_t span = 0;
@@ -378,7 +413,14 @@ struct Stage {
             }
             offs[g.idx.size()] = acc;
         }
-        if (njobs) {
+        if (collects) {
+            for (size_t k = 0; k < njobs; k++) {  // {hit counter: 0, target, lists}
+                const uint64_t words[3] = {0ull, targets[k], lists[k] ? 1ull : 0ull};
+                std::memcpy(meta + thresh_at + sizeof words * k, words, sizeof words);
+            }
+            const uint32_t head[4] = {0u, 0u, (uint32_t)list_cap, 0u};  // appended (64 bits), capacity
+            std::memcpy(meta + list_at, head, kBatchListHead);
+        } else if (njobs) {
             std::memset(meta + thresh_at, 0xFF, job_words_bytes() * njobs);
             for (size_t k = 0; by_digits && k < njobs; k++)  // {bound: all ones, target}
                 std::memcpy(meta + thresh_at + 16 * k + 8, &targets[k], 8);

@@ -38,6 +38,9 @@ GPUHASH_MAX_MSG = 1 << 20
 GPUHASH_COLLECT_MAX = 1 << 20
 GPUHASH_BATCH_MAX_JOBS = 1 << 16
 GPUHASH_BATCH_MAX_SPAN = 1 << 38
+# Engine.collect_below_batch: the room of a job given without a cap.  The batch is built for sparse
+# hits and its output arrays hold the sum of the jobs' caps, so the default is small.
+BATCH_COLLECT_CAP = 256
 LAYOUT_AUTO, LAYOUT_UNIFORM, LAYOUT_CLASSIC, LAYOUT_LANETABLE = 0, 1, 2, 3
 # OR-able flags: tail-digit launches always / never (include/gpuhash.h)
 LAYOUT_TAIL_ALWAYS, LAYOUT_TAIL_NEVER = 16, 32
@@ -52,6 +55,7 @@ EXPORTED = [
     "gpuhash_collect_below", "gpuhash_collect_below_ex",
     "gpuhash_min_batch", "gpuhash_min_batch_ex",
     "gpuhash_first_below_batch", "gpuhash_first_below_batch_ex",
+    "gpuhash_collect_below_batch", "gpuhash_collect_below_batch_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
@@ -178,6 +182,15 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
                                                  ctypes.POINTER(u64), ctypes.POINTER(u64),
                                                  ctypes.POINTER(ctypes.c_int)]
     lib.gpuhash_first_below_batch_ex.restype = ctypes.c_int
+    lib.gpuhash_collect_below_batch.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
+                                                ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(sz),
+                                                ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.gpuhash_collect_below_batch.restype = ctypes.c_int
+    lib.gpuhash_collect_below_batch_ex.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
+                                                   ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_uint32,
+                                                   ctypes.POINTER(sz), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                   ctypes.POINTER(u64)]
+    lib.gpuhash_collect_below_batch_ex.restype = ctypes.c_int
     lib.gpuhash_hash_range.argtypes = [vp, u8p, sz, u64, u64, vp]
     lib.gpuhash_hash_range.restype = ctypes.c_int
     lib.gpuhash_hash_cpu.argtypes = [u8p, sz, u64]
@@ -386,6 +399,54 @@ class Engine:
         """How many nonces of the inclusive [lower, upper] have Hash(msg, n) <= target:
         collect_below with cap = 0, which lists nothing."""
         return self.collect_below(msg, lower, upper, target, cap=0, rchunk=rchunk)[0]
+
+    def collect_below_batch(self, jobs, rchunk: int = 0) -> list[tuple[int, list[tuple[int, int]]]]:
+        """Many independent collections in one call: entry k is what collect_below(*jobs[k]) returns,
+        (total, hits), for jobs given as (msg, lower, upper, target[, cap]); a job without a cap
+        has room for BATCH_COLLECT_CAP hits, and cap = 0 only counts (gpuhash_collect_below_batch_ex;
+        one scan launch per kernel variant among all the jobs).  Every nonce of every job is hashed;
+        built for sparse hits.  Jobs are checked before calling in, as for first_below_batch, and
+        a cap as for collect_below (ValueError, TypeError)."""
+        jobs = [tuple(j) for j in jobs]
+        caps = []
+        for k, j in enumerate(jobs):
+            if len(j) not in (4, 5):
+                raise ValueError(f"job {k} is not (msg, lower, upper, target[, cap])")
+            cap = j[4] if len(j) == 5 else BATCH_COLLECT_CAP
+            if isinstance(cap, bool) or not isinstance(cap, int):
+                raise TypeError(f"jobs[{k}].cap must be an int, got {type(cap).__name__}")
+            if not 0 <= cap <= GPUHASH_COLLECT_MAX:
+                raise ValueError(f"jobs[{k}].cap={cap} outside [0, GPUHASH_COLLECT_MAX]")
+            caps.append(cap)
+        n, data, off, lower, upper, target = self._batch_arrays([j[:4] for j in jobs], rchunk, 4)
+        out_off = (ctypes.c_size_t * (n + 1))()
+        for k, cap in enumerate(caps):
+            out_off[k + 1] = out_off[k] + cap
+        room = out_off[n]
+        nonces = (ctypes.c_uint64 * room)() if room else None
+        hashes = (ctypes.c_uint64 * room)() if room else None
+        totals = (ctypes.c_uint64 * n)()
+        rc = self._lib.gpuhash_collect_below_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper,
+                                                      target, rchunk, out_off, nonces, hashes, totals)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_collect_below_batch")
+        out = []
+        for k in range(n):
+            at, held = out_off[k], min(caps[k], int(totals[k]))
+            out.append((int(totals[k]), [(int(hashes[at + i]), int(nonces[at + i])) for i in range(held)]))
+        return out
+
+    def count_below_batch(self, jobs, rchunk: int = 0) -> list[int]:
+        """How many nonces of each job's range have a hash <= its target, for jobs given as (msg,
+        lower, upper, target): collect_below_batch with no room at all (a null out_off), which
+        lists nothing."""
+        n, data, off, lower, upper, target = self._batch_arrays(jobs, rchunk, 4)
+        totals = (ctypes.c_uint64 * n)()
+        rc = self._lib.gpuhash_collect_below_batch_ex(self._ctx, ctypes.addressof(data), off, n, lower, upper,
+                                                      target, rchunk, None, None, None, totals)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_collect_below_batch")
+        return [int(t) for t in totals]
 
     def hash_range(self, msg, lower: int, count: int):
         """numpy uint64 array of Hash(msg, lower + i), computed by the scan kernels."""

@@ -315,6 +315,55 @@ int gpuhash_first_below_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const si
                                  const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
                                  uint32_t rchunk, uint64_t *out_hashes, uint64_t *out_nonces, int *out_found);
 
+/* njobs independent gpuhash_collect_below collections in one call (a miner holding many short work
+ * units, each with its own message, range and share target; a service counting hits per message
+ * to calibrate a difficulty): out_totals[k] is exactly what gpuhash_collect_below(ctx, msg_k,
+ * len_k, lower[k], upper[k], target[k], ...) reports as *out_total, the EXACT number of nonces of
+ * the job's range whose hash is <= target[k].  Job k's room in the two output arrays is
+ * cap_k = out_off[k+1] - out_off[k] entries from out_off[k] on: out_nonces[out_off[k] + i] and
+ * out_hashes[out_off[k] + i] for i < min(cap_k, total_k) are the LOWEST min(cap_k, total_k)
+ * qualifying nonces of job k, ascending by nonce, and their hashes -- never merely some qualifying
+ * nonces -- under every layout policy, tail flag and rchunk, however many context entries ran and
+ * in whatever order the jobs are listed.  Entries from min(cap_k, total_k) on are untouched.  The
+ * comparison is <=, a nonce of 2^64-1 is a legal hit, and the jobs are independent: two jobs of one
+ * message with different targets or overlapping ranges are two collections.
+ * out_off has njobs + 1 entries and never decreases; out_off == NULL means every cap_k = 0, a pure
+ * count, and out_nonces and out_hashes may then be null.
+ * A gpuhash_collect_below call costs ~0.1 ms whatever its range (three launches, two waits); a
+ * batch runs ONE scan launch per kernel variant among all its jobs.  Every job
+ * has an exact hit counter of its own on the device; the hits of all listing jobs go to ONE device
+ * list per context entry of GPUHASH_COLLECT_MAX entries (24 MB, allocated on the entry's first
+ * listing batch; env GPUHASH_COLLECT_BUFFER=<entries> overrides the size, as for
+ * gpuhash_collect_below).  Built for SPARSE hits: a job all of whose hits found room in the list
+ * is answered from it; a job cut short by a full list is run again alone, after the batch, as
+ * gpuhash_collect_below runs it, so a batch dense enough to overflow the list costs as much as
+ * the loop of single calls does, and is still exact.  Raising GPUHASH_COLLECT_BUFFER is the remedy.
+ * The flat arrays, msg_off, empty messages, GPUHASH_BATCH_MAX_JOBS, GPUHASH_BATCH_MAX_SPAN, the
+ * sub-batches under GPUHASH_BATCH_BYTES (which counts the launch metadata and the K+W tables, not
+ * the fixed list) and the runs of whole jobs over the context's entries are as for
+ * gpuhash_min_batch.  Whole-call argument errors, detected before any use of ctx's contents and
+ * before anything is written to the outputs, deterministic: everything
+ * gpuhash_first_below_batch refuses, and GPUHASH_EINVAL for a null out_totals, an out_off that
+ * decreases, any cap_k > GPUHASH_COLLECT_MAX, and out_off[njobs] > 0 with a null out_nonces or
+ * out_hashes.
+ * Every nonce of every job is hashed, there is no early exit: afterwards
+ * gpuhash_last_stats().nonces is the saturating sum of the jobs' spans and .launches every scan
+ * launch that ran, re-runs included; gpuhash_last_launches gives one record per kernel variant per
+ * context entry per sub-batch with `lo`, `hi` job indices as for gpuhash_min_batch, and every
+ * launch of a re-run of job k carries lo == hi == k.  Threading, device-guard behaviour, errors and
+ * the no-exception rule are as for gpuhash_min.  Replaces nothing in the reference (its protocol
+ * has no target field). */
+int gpuhash_collect_below_batch(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                                const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
+                                const size_t *out_off, uint64_t *out_nonces, uint64_t *out_hashes,
+                                uint64_t *out_totals);
+
+/* Same batch, caller-chosen work-item granularity (as gpuhash_min_ex). */
+int gpuhash_collect_below_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                                   const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
+                                   uint32_t rchunk, const size_t *out_off, uint64_t *out_nonces,
+                                   uint64_t *out_hashes, uint64_t *out_totals);
+
 /* out[i] = Hash(msg, lower + i) for i < count, computed on the first device by the
  * SAME kernels as gpuhash_min (per-nonce dump mode).  count <= 2^26; lower + count - 1
  * must not wrap.  Parity/diagnostic API (batch form of hash.go:11-15). */

@@ -224,5 +224,82 @@ func (e *Engine) FirstBelowBatch(jobs []Job, targets []uint64) (hashes, nonces [
 	return hashes, nonces, found, nil
 }
 
+// JobHits is one job's answer of CollectBelowBatch: the exact number of qualifying nonces, and the
+// lowest min(cap, Total) of them, ascending, with their hashes.
+type JobHits struct {
+	Total  uint64
+	Nonces []uint64
+	Hashes []uint64
+}
+
+// CollectBelowBatch answers many independent collections in one call: out[k] is exactly what
+// CollectBelow(jobs[k].Data, jobs[k].Lower, jobs[k].Upper, targets[k], caps[k]) returns -- the
+// exact hit count and the lowest caps[k] hits.  For a miner that holds many short work units,
+// each with its own share target: the engine runs one kernel launch per kernel variant among
+// all the jobs, where a loop of CollectBelow calls pays ~0.1 ms per call.  Built for sparse
+// hits.  caps == nil only counts; else len(caps) and len(targets) must equal len(jobs) and
+// every cap be at most GPUHASH_COLLECT_MAX; the other limits are MinBatch's.
+func (e *Engine) CollectBelowBatch(jobs []Job, targets []uint64, caps []int) (out []JobHits, err error) {
+	n := len(jobs)
+	if n == 0 || n > int(C.GPUHASH_BATCH_MAX_JOBS) || len(targets) != n || (caps != nil && len(caps) != n) {
+		return nil, rcErr(C.GPUHASH_EINVAL)
+	}
+	off := make([]C.size_t, n+1)
+	lower := make([]C.uint64_t, n)
+	upper := make([]C.uint64_t, n)
+	target := make([]C.uint64_t, n)
+	totals := make([]uint64, n)
+	msgs := make([]byte, 0, 64*n)
+	for k, j := range jobs {
+		msgs = append(msgs, j.Data...)
+		off[k+1] = C.size_t(len(msgs))
+		lower[k] = C.uint64_t(j.Lower)
+		upper[k] = C.uint64_t(j.Upper)
+		target[k] = C.uint64_t(targets[k])
+	}
+	var p *C.uint8_t
+	if len(msgs) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&msgs[0]))
+	}
+	var outOff []C.size_t
+	var po *C.size_t
+	var pn, ph *C.uint64_t
+	var nonces, hashes []uint64
+	if caps != nil {
+		outOff = make([]C.size_t, n+1)
+		for k, c := range caps {
+			if c < 0 || c > int(C.GPUHASH_COLLECT_MAX) {
+				return nil, rcErr(C.GPUHASH_EINVAL)
+			}
+			outOff[k+1] = outOff[k] + C.size_t(c)
+		}
+		po = &outOff[0]
+		if room := int(outOff[n]); room > 0 {
+			nonces = make([]uint64, room)
+			hashes = make([]uint64, room)
+			pn = (*C.uint64_t)(unsafe.Pointer(&nonces[0]))
+			ph = (*C.uint64_t)(unsafe.Pointer(&hashes[0]))
+		}
+	}
+	rc := C.gpuhash_collect_below_batch(e.ctx, p, &off[0], C.size_t(n), &lower[0], &upper[0], &target[0], po, pn, ph, (*C.uint64_t)(unsafe.Pointer(&totals[0])))
+	if err = rcErr(rc); err != nil {
+		return nil, err
+	}
+	out = make([]JobHits, n)
+	for k := range out {
+		out[k].Total = totals[k]
+		if caps == nil {
+			continue
+		}
+		at, held := int(outOff[k]), caps[k]
+		if totals[k] < uint64(held) {
+			held = int(totals[k])
+		}
+		out[k].Nonces = nonces[at : at+held]
+		out[k].Hashes = hashes[at : at+held]
+	}
+	return out, nil
+}
+
 // Close releases the devices.
 func (e *Engine) Close() { C.gpuhash_close(e.ctx) }

@@ -6,8 +6,10 @@ code bytes, its register and segment figures, and a SHA-256 of its whole metadat
     python tools/kernel_manifest.py                 # the product objects of bitcoin-miner_amd/build
     python tools/kernel_manifest.py build/tie_*.o   # or the objects named
 
-tests/golden/kernel_manifest.txt is this tool's output for the product objects, and
-tests/test_codegen.py holds the build against it.  The objects must exist (make builds them).
+tests/golden/kernel_manifest.txt is this tool's output for the product objects up to MODE 5, and
+tests/test_codegen.py holds the build against it; tests/golden/kernel_manifest_collect_batch.txt is
+its output for build/kernels_{plain,ut,misc}_collectbatch.o (MODE 6), held by
+tests/test_collect_below_batch_cpu.py.  The objects must exist (make builds them).
 """
 import glob
 import hashlib
@@ -81,5 +83,7 @@ def manifest(objs):
 
 
 if __name__ == "__main__":
-    objs = sys.argv[1:] or sorted(o for o in glob.glob(os.path.join(BUILD, "kernels*.o")) if not o.endswith(".dev.o"))
+    # the default is kernel_manifest.txt's set: the MODE 6 objects have a fixture of their own
+    objs = sys.argv[1:] or sorted(o for o in glob.glob(os.path.join(BUILD, "kernels*.o"))
+                                  if not o.endswith((".dev.o", "_collectbatch.o")))
     print("\n".join(manifest(objs)))
