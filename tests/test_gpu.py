@@ -43,9 +43,10 @@ def test_config1_miner_request(engine):
 
 
 def variant_cases():
-    """(msg, lower, count) windows that straddle digit-count and block boundaries for
-    message lengths 0..140, so every (J, C2, EX) kernel variant and both lane-word
-    placements run."""
+    """(msg, lower, count) windows with a seeded random digit count per message length 0..140,
+    most of them across a digit-count boundary, and fixed windows at 0, at 10^19 and at the top
+    of uint64.  Which kernels they reach is not checked here: tests/test_gpu_variant_matrix.py
+    runs every compiled (J, C2, EX, MODE) kernel and asserts that it ran."""
     rng = random.Random(42)
     cases = []
     for mlen in list(range(0, 70)) + list(range(100, 141, 3)):

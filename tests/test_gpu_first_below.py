@@ -57,8 +57,10 @@ def test_errors_are_loud(engine):
 
 def variant_cases():
     """The window family of test_gpu.py's test_hash_range_bit_exact, restated: (msg, lower,
-    count) windows that straddle digit-count and block boundaries for message lengths
-    0..140, so every (J, C2, EX) kernel variant and both lane-word placements run."""
+    count) windows with a seeded random digit count per message length 0..140, most of them
+    across a digit-count boundary, and fixed windows at 0, at 10^19 and at the top of uint64.
+    test_every_variant checks the layout families these reach, not every J: the guarantee that
+    every compiled (J, C2, EX, MODE) kernel runs is tests/test_gpu_variant_matrix.py's."""
     rng = random.Random(42)
     cases = []
     for mlen in list(range(0, 70)) + list(range(100, 141, 3)):
