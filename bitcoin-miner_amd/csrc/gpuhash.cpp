@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "collect.h"
+#include "control.h"
 #include "kernels.h"
 #include "plan.h"
 #include "stage.h"
@@ -60,6 +61,14 @@ struct Dev {
     size_t clk_cap = 0;  // words
     std::vector<hipEvent_t> ev;
     hipEvent_t done = nullptr;  // blocking-sync event: the end of a call's work (host_wait)
+    // the control side (control.h): a second stream that never carries a kernel, for the copies
+    // that must run while a persistent grid holds the device -- the drain word onto the stage's
+    // work counters, and the counters back for gpuhash_progress
+    Control* ctl = nullptr;          // the context's
+    hipStream_t ctl_stream = nullptr;
+    uint8_t* h_prog = nullptr;       // pinned, kControlCopyBytes: the head of d_meta, for progress
+    hipEvent_t uploaded = nullptr;   // on `stream`, after the stage upload: the control copies wait for it
+    hipEvent_t prog_done = nullptr;  // on ctl_stream, after a progress copy
     int wait_mode = 0;          // HostWait
     // per-call results
     int rc = GPUHASH_OK;
@@ -101,6 +110,7 @@ struct gpuhash_ctx {
     // concurrent callers, e.g. several goroutines sharing an Engine, are serialised here.
     std::mutex mu;
     std::vector<Dev> devs;
+    std::unique_ptr<Control> ctl;  // cancel latch and progress mailbox: used without `mu`
     int policy = kLayoutAuto;
     gpuhash_stats last{};
     std::vector<gpuhash_launch_record> recs;
@@ -158,7 +168,84 @@ static int host_wait_mode() {
     return kWaitPoll;
 }
 
-static int host_wait(Dev& d) {
+// While it polls, the waiting thread also serves the context's control side (control.h): it
+// drains the stage's work counters once when the cancel latch is seen, and answers progress
+// requests from a copy of those counters.  Both are copies on the entry's control stream, which
+// never carries a kernel, enqueued only after the host has seen the stage's upload complete (the
+// upload zeroes the counters) and ordered after nothing else.  They are kControlCopyBytes long at
+// least, because that is what makes the runtime hand them to a copy engine, which runs beside
+// the persistent grid; a shorter copy is a shader blit and waits for the grid (control.h).
+// The drain is therefore the head of the pinned metadata image, uploaded again with the drain
+// word in the counters: the prefix offsets and descriptors it rewrites are the bytes already
+// there, and what else it touches -- the clock words, the p-table room, a batch's per-job words
+// and list -- only feeds results, which a cancelled call discards; no index or bound is among
+// them but a list's head, which it sets back to empty.
+// Nothing is enqueued unless somebody cancelled or asked.  `stream` and `event` do not poll: there
+// the latch is honoured and progress known at launch boundaries only.
+static int poll_wait(Dev& d, const Stage& st) {
+    Control& C = *d.ctl;
+    const size_t slot = (size_t)d.shard, ng = st.groups.size();
+    // both buffers hold max(their stage bytes, kControlCopyBytes) at least (stage_upload), and a
+    // stage's bytes include every counter block
+    const size_t drain_bytes = std::max(kControlCopyBytes, kCounterBytes * ng);
+    bool drained = false, copying = false;
+    uint64_t ticket = 0;
+    C.poll_enter(slot);
+    int rc = GPUHASH_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipEventQuery(d.done);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) { rc = GPUHASH_EHIP; break; }
+        const bool asked = !copying && (ticket = C.wanted(slot)) != 0;
+        const bool cancel = !drained && C.observe();
+        if ((cancel || asked) && hipEventQuery(d.uploaded) != hipSuccess) {
+            // the stage has not begun (entries that share a device run one after the other): none
+            // of its work is handed out, and its drain has to wait for the upload
+            if (asked) C.publish(slot, ticket, 0);
+        } else if (cancel || asked) {
+            if (cancel) {
+                drained = true;  // one drain per stage: later groups find their counters drained
+                for (const StageGroup& G : st.groups) std::memcpy(d.h_meta + G.work_at, &kDrainWord, sizeof kDrainWord);
+                if (hipStreamWaitEvent(d.ctl_stream, d.uploaded, 0) != hipSuccess ||
+                    hipMemcpyAsync(d.d_meta, d.h_meta, drain_bytes, hipMemcpyHostToDevice, d.ctl_stream) != hipSuccess) {
+                    rc = GPUHASH_EHIP;
+                    break;
+                }
+            }
+            if (asked) {
+                if (hipStreamWaitEvent(d.ctl_stream, d.uploaded, 0) != hipSuccess ||
+                    hipMemcpyAsync(d.h_prog, d.d_meta, kControlCopyBytes, hipMemcpyDeviceToHost, d.ctl_stream) != hipSuccess ||
+                    hipEventRecord(d.prog_done, d.ctl_stream) != hipSuccess) {
+                    rc = GPUHASH_EHIP;
+                    break;
+                }
+                copying = true;
+            }
+        } else if (copying) {
+            const hipError_t p = hipEventQuery(d.prog_done);
+            if (p == hipSuccess) {
+                uint64_t part = 0;  // a group whose counter lies past the copy counts when the stage is over
+                for (const StageGroup& G : st.groups) {
+                    if (G.work_at + sizeof(uint64_t) > kControlCopyBytes) break;
+                    uint64_t counter;
+                    std::memcpy(&counter, d.h_prog + G.work_at, sizeof counter);
+                    part = sat_add(part, handed_out(G.nonces, counter, G.total));
+                }
+                C.publish(slot, ticket, part);
+                copying = false;
+            } else if (p != hipErrorNotReady) { rc = GPUHASH_EHIP; break; }
+        }
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(500))
+            std::this_thread::sleep_for(std::chrono::microseconds(100));
+    }
+    C.poll_exit(slot);
+    // no control copy outlives the stage it was aimed at: the next upload reuses these bytes
+    if ((drained || copying) && hipStreamSynchronize(d.ctl_stream) != hipSuccess) rc = GPUHASH_EHIP;
+    return rc;
+}
+
+static int host_wait(Dev& d, const Stage& st) {
     if (d.wait_mode == kWaitStream) {
         HIPCHK(hipStreamSynchronize(d.stream));
         return GPUHASH_OK;
@@ -168,19 +255,13 @@ static int host_wait(Dev& d) {
         HIPCHK(hipEventSynchronize(d.done));
         return GPUHASH_OK;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipEventQuery(d.done);
-        if (q == hipSuccess) return GPUHASH_OK;
-        if (q != hipErrorNotReady) return GPUHASH_EHIP;
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(500))
-            std::this_thread::sleep_for(std::chrono::microseconds(100));
-    }
+    return poll_wait(d, st);
 }
 
-static int dev_init(Dev& d, int ord, int shard) {
+static int dev_init(Dev& d, int ord, int shard, Control* ctl) {
     d.ord = ord;
     d.shard = shard;
+    d.ctl = ctl;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(ord));
     HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
@@ -196,6 +277,16 @@ static int dev_init(Dev& d, int ord, int shard) {
     if (hipHostMalloc(&d.h_best, sizeof(Cand), hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
     if (hipHostMalloc(&d.h_nhit, sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
     HIPCHK(hipMemset(d.d_ncand, 0, sizeof(unsigned int)));
+    // The control stream takes the highest stream priority: the runtime maps the streams of one
+    // priority onto a few hardware queues that they share, and a copy on a stream that shares its
+    // queue with a stream whose grid is resident (this context's, or another's in the process)
+    // waits for that grid.  No kernel ever runs at this priority, so no such queue holds one.
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(hipStreamCreateWithPriority(&d.ctl_stream, hipStreamNonBlocking, greatest));
+    HIPCHK(hipEventCreateWithFlags(&d.uploaded, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&d.prog_done, hipEventDisableTiming));
+    if (hipHostMalloc(&d.h_prog, kControlCopyBytes, hipHostMallocDefault) != hipSuccess) return GPUHASH_ENOMEM;
     return GPUHASH_OK;
 }
 
@@ -204,9 +295,14 @@ static void dev_free(Dev& d) {
     DeviceGuard guard;
     hipSetDevice(d.ord);
     if (d.stream) hipStreamSynchronize(d.stream);
+    if (d.ctl_stream) hipStreamSynchronize(d.ctl_stream);
     for (auto e : d.ev) hipEventDestroy(e);
     d.ev.clear();
     if (d.done) hipEventDestroy(d.done);
+    if (d.uploaded) hipEventDestroy(d.uploaded);
+    if (d.prog_done) hipEventDestroy(d.prog_done);
+    if (d.h_prog) hipHostFree(d.h_prog);
+    if (d.ctl_stream) hipStreamDestroy(d.ctl_stream);
     if (d.d_thresh) hipFree(d.d_thresh);
     if (d.d_ncand) hipFree(d.d_ncand);
     if (d.d_best) hipFree(d.d_best);
@@ -294,9 +390,10 @@ constexpr ModeWiring kWiring[] = {
 // dev_run, phase 1: reserves the entry's buffers, writes and uploads the launch metadata in one
 // copy, and has the device build the tables.  grids[g] = workgroups of group g.
 static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector<unsigned int>& grids) {
-    const size_t ng = st.groups.size(), meta = std::max<size_t>(st.bytes, 64 * 1024);
+    // both metadata buffers hold kControlCopyBytes at least: a drain copies that much (poll_wait)
+    const size_t ng = st.groups.size(), meta = std::max<size_t>(st.bytes, kControlCopyBytes);
     int rc;
-    const size_t host_meta = std::max<size_t>(st.upload_bytes, 64 * 1024);  // a batch's list is the device's alone
+    const size_t host_meta = std::max<size_t>(st.upload_bytes, kControlCopyBytes);  // a batch's list is the device's alone
     if ((rc = grow(d.d_meta, d.meta_cap, meta)) || (rc = grow(d.h_meta, d.h_meta_cap, host_meta, true))) return rc;
     st.fill(d.h_meta);
     size_t sumgrid = 0;
@@ -321,6 +418,7 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
         d.ev.push_back(e);
     }
     HIPCHK(hipMemcpyAsync(d.d_meta, d.h_meta, st.upload_bytes, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(hipEventRecord(d.uploaded, d.stream));  // the counters are zeroed: a drain may follow (poll_wait)
     for (const StageTab& t : st.tabs)
         HIPCHK(launch_ktab(reinterpret_cast<const LaunchDesc*>(d.d_meta + t.desc_byte), d.d_ktab + t.off,
                            t.R, d.stream));
@@ -397,7 +495,12 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
     const size_t result_bytes = w.collects ? sizeof(unsigned long long) : sizeof(Cand);
     if (!w.batch) HIPCHK(hipMemcpyAsync(d.h_best, result, result_bytes, hipMemcpyDeviceToHost, d.stream));
     HIPCHK(hipMemcpyAsync(d.h_clk, d.d_meta, kCounterBytes * st.groups.size(), hipMemcpyDeviceToHost, d.stream));
-    if (int rc = host_wait(d)) return rc;
+    if (int rc = host_wait(d, st)) return rc;
+    // whatever the wait brought back is discarded once the call has seen the latch
+    if (d.ctl->observe()) return GPUHASH_ECANCELED;
+    uint64_t stage_nonces = 0;
+    for (const StageGroup& G : st.groups) stage_nonces = sat_add(stage_nonces, G.nonces);
+    d.ctl->stage_done((size_t)d.shard, stage_nonces);
     for (size_t g = 0; g < st.groups.size(); g++) {
         const StageGroup& G = st.groups[g];
         float ms = 0;
@@ -521,7 +624,18 @@ struct Call {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     gpuhash_stats st{};
 
-    explicit Call(gpuhash_ctx* c) : ctx(c) { ctx->recs.clear(); }
+    // total: the call's nonce count, saturating (gpuhash_progress)
+    Call(gpuhash_ctx* c, uint64_t total) : ctx(c) {
+        ctx->recs.clear();
+        ctx->ctl->begin_call(total);
+    }
+    ~Call() { ctx->ctl->end_call(); }
+    Call(const Call&) = delete;
+    Call& operator=(const Call&) = delete;
+
+    // The cancel latch, read at call entry and before every run of the entries (run_each): every
+    // slice, sub-batch and collector re-run.
+    bool cancelled() { return ctx->ctl->observe(); }
 
     // Runs `job` over the batch: on the caller's thread when it is one sub-range, else each on a
     // host thread of its own.  Takes the entries' records and times; returns the first failure.
@@ -539,6 +653,7 @@ struct Call {
     // thread of its own.
     template <class F>
     int run_each(size_t n, F&& one) {
+        if (cancelled()) return GPUHASH_ECANCELED;
         for (auto& d : ctx->devs) d.reset();
         if (n == 1) {
             one((size_t)0);
@@ -622,8 +737,9 @@ static int open_impl(const int* devices, int ndevices, gpuhash_ctx** out) {
         delete c;
     });
     ctx->devs.resize(ords.size());
+    ctx->ctl.reset(new Control(ords.size()));
     for (size_t i = 0; i < ords.size(); i++) {
-        int rc = dev_init(ctx->devs[i], ords[i], (int)i);
+        int rc = dev_init(ctx->devs[i], ords[i], (int)i, ctx->ctl.get());
         if (rc) return rc;
     }
     *out = ctx.release();
@@ -676,6 +792,19 @@ int gpuhash_set_layout_policy(gpuhash_ctx* ctx, int policy) {
     return GPUHASH_OK;
 }
 
+// The nonces of the inclusive [lower, upper], saturating.
+static uint64_t span_of(uint64_t lower, uint64_t upper) {
+    const uint64_t s = upper - lower;
+    return s == ~0ull ? ~0ull : s + 1;
+}
+
+// The sum of a batch's spans, saturating.
+static uint64_t spans_of(size_t njobs, const uint64_t* lower, const uint64_t* upper) {
+    uint64_t n = 0;
+    for (size_t k = 0; k < njobs; k++) n = sat_add(n, upper[k] - lower[k] + 1);  // <= GPUHASH_BATCH_MAX_SPAN each
+    return n;
+}
+
 // The slice loop of gpuhash_min_ex and gpuhash_first_below_ex (kScanFirst, where out_found is
 // set and the loop stops after the first slice that has a hit).  Searches longer than a slice
 // (stage.h, slice_width) run as consecutive slices, each sharded over the context's devices,
@@ -684,7 +813,8 @@ static int search(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_t
                   uint32_t rchunk, const ScanJob& job, uint64_t* out_hash, uint64_t* out_nonce,
                   int* out_found) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, span_of(lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     const uint64_t slice = slice_width(ctx->devs.size());
     const bool first = job.mode == kScanFirst;
     uint64_t bh = ~0ull, bn = ~0ull;
@@ -755,7 +885,8 @@ static int collect(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uint64_
                    uint64_t target, uint32_t rchunk, uint64_t* out_nonces, uint64_t* out_hashes, size_t cap,
                    uint64_t* out_total) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, span_of(lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     const uint32_t buffer = collect_buffer();
     auto split = [&](uint64_t lo, uint64_t hi, std::vector<SubRange>& batch) {
         split_slice(msg_len, lo, hi, (int)ctx->devs.size(), ctx->policy, batch);
@@ -807,7 +938,8 @@ static int min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_of
                      const uint64_t* lower, const uint64_t* upper, uint32_t rchunk, uint64_t* out_hashes,
                      uint64_t* out_nonces) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, spans_of(njobs, lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
     const int policy = ctx->policy;
     auto plan = [&](size_t k) {
@@ -869,7 +1001,8 @@ static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t
                              const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
                              uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, spans_of(njobs, lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
     std::vector<uint8_t> rf(njobs);
     const int policy = ctx->policy;
@@ -975,7 +1108,8 @@ static int collect_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size
                                uint32_t rchunk, const size_t* out_off, uint64_t* out_nonces, uint64_t* out_hashes,
                                uint64_t* out_totals) {
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, spans_of(njobs, lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     const uint32_t buffer = collect_buffer();
     std::vector<JobHits> res(njobs);  // the outputs are written only when all ran
     std::vector<size_t> caps(njobs, 0);
@@ -1089,7 +1223,8 @@ int gpuhash_hash_range(gpuhash_ctx* ctx, const uint8_t* msg, size_t msg_len, uin
     if (count > (1ull << 26) || lower + (count - 1) < lower) return GPUHASH_EINVAL;
     if (msg_len > GPUHASH_MAX_MSG) return GPUHASH_ETOOLONG;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx);
+    Call call(ctx, count);
+    if (call.cancelled()) return GPUHASH_ECANCELED;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(ctx->devs[0].ord));
     ScanJob job{kScanDump};
@@ -1122,6 +1257,24 @@ int gpuhash_last_launches(const gpuhash_ctx* ctx, gpuhash_launch_record* out, in
     return n;
 }
 
+int gpuhash_cancel(gpuhash_ctx* ctx) {
+    if (!ctx) return GPUHASH_EINVAL;
+    ctx->ctl->cancel();  // one lock-free atomic store: async-signal-safe
+    return GPUHASH_OK;
+}
+
+int gpuhash_resume(gpuhash_ctx* ctx) {
+    if (!ctx) return GPUHASH_EINVAL;
+    ctx->ctl->resume();
+    return GPUHASH_OK;
+}
+
+int gpuhash_progress(gpuhash_ctx* ctx, uint64_t* out_done, uint64_t* out_total) {
+    if (!ctx || !out_done || !out_total) return GPUHASH_EINVAL;
+    ctx->ctl->progress(out_done, out_total);  // no HIP call, no ctx->mu: the call's waiting threads answer
+    return GPUHASH_OK;
+}
+
 void gpuhash_close(gpuhash_ctx* ctx) {
     if (!ctx) return;
     for (auto& d : ctx->devs) dev_free(d);
@@ -1136,6 +1289,7 @@ const char* gpuhash_strerror(int rc) {
         case GPUHASH_EHIP: return "HIP runtime error or kernel launch failure";
         case GPUHASH_ETOOLONG: return "message longer than GPUHASH_MAX_MSG";
         case GPUHASH_ENOMEM: return "out of device or host memory";
+        case GPUHASH_ECANCELED: return "search cancelled (gpuhash_cancel; gpuhash_resume clears it)";
         default: return "unknown gpuhash error";
     }
 }

@@ -26,15 +26,71 @@
  *                                         of the job's lowest CAP (default 256) nonces whose hash is
  *                                         <= TARGET, ascending, from ONE gpuhash_collect_below_batch call
  *   gpuhash_cli --version
- * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch.
+ * --progress in front of any of the searches prints "<done> <total>" (gpuhash_progress) on stderr
+ * about once a second, from a second thread.
+ * SIGINT and SIGTERM cancel the search in flight (gpuhash_cancel, from the handler): the run then
+ * prints "Cancelled" on stderr, nothing on stdout, and exits 130.
+ * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch, 130 cancelled.
  */
 #define _POSIX_C_SOURCE 200809L /* getline, strtok_r */
 #include <inttypes.h>
+#include <pthread.h>
+#include <signal.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include "gpuhash.h"
+
+/* The context the signal handler cancels.  A signal that arrives before it is open is kept in
+ * g_signalled and turned into the cancel as soon as it is (the latch then fails the first call). */
+static gpuhash_ctx *volatile g_ctx;
+static volatile sig_atomic_t g_signalled;
+static int g_progress;
+
+static void on_signal(int sig) {
+    (void)sig;
+    g_signalled = 1;
+    gpuhash_ctx *ctx = g_ctx;
+    if (ctx) gpuhash_cancel(ctx); /* one atomic store: async-signal-safe */
+}
+
+static void *progress_main(void *arg) {
+    (void)arg;
+    for (;;) {
+        struct timespec second = {1, 0};
+        nanosleep(&second, NULL);
+        uint64_t done = 0, total = 0;
+        gpuhash_ctx *ctx = g_ctx;
+        if (!ctx) return NULL;
+        if (gpuhash_progress(ctx, &done, &total) == GPUHASH_OK && total)
+            fprintf(stderr, "%" PRIu64 " %" PRIu64 "\n", done, total);
+    }
+}
+
+static pthread_t g_progress_thread;
+
+/* gpuhash_open for this program: the context becomes the signal handler's, and --progress's. */
+static int open_ctx(gpuhash_ctx **out) {
+    const int rc = gpuhash_open(NULL, 0, out);
+    if (rc) return rc;
+    g_ctx = *out;
+    if (g_signalled) gpuhash_cancel(*out);
+    if (g_progress && pthread_create(&g_progress_thread, NULL, progress_main, NULL) != 0) g_progress = 0;
+    return rc;
+}
+
+static void close_ctx(gpuhash_ctx *ctx) {
+    signal(SIGINT, SIG_DFL); /* from here on a signal ends the program as it would any other */
+    signal(SIGTERM, SIG_DFL);
+    g_ctx = NULL; /* the handler and the progress thread stop using it */
+    if (g_progress) {
+        pthread_cancel(g_progress_thread); /* it is in nanosleep, or about to be */
+        pthread_join(g_progress_thread, NULL);
+    }
+    gpuhash_close(ctx);
+}
 
 static int parse_u64(const char *s, uint64_t *out) {
     char *end = NULL;
@@ -46,6 +102,10 @@ static int parse_u64(const char *s, uint64_t *out) {
 }
 
 static int fail(const char *what, int rc) {
+    if (rc == GPUHASH_ECANCELED) {
+        fprintf(stderr, "Cancelled\n");
+        return 130;
+    }
     fprintf(stderr, "%s: %s (rc=%d)\n", what, gpuhash_strerror(rc), rc);
     return 3;
 }
@@ -175,12 +235,12 @@ static int batch_main(const char *path, int below) {
         n = (uint64_t *)malloc(njobs * sizeof *n);
         found = (int *)malloc(njobs * sizeof *found);
         gpuhash_ctx *ctx = NULL;
-        int rc = h && n && found ? gpuhash_open(NULL, 0, &ctx) : GPUHASH_ENOMEM;
+        int rc = h && n && found ? open_ctx(&ctx) : GPUHASH_ENOMEM;
         if (rc) {
             status = fail("gpuhash_open", rc);
         } else if (below == 2) {
             status = batch_all_main(ctx, msgs, off, njobs, lower, upper, target, caps);
-            gpuhash_close(ctx);
+            close_ctx(ctx);
         } else if (below) {
             rc = gpuhash_first_below_batch(ctx, msgs, off, njobs, lower, upper, target, h, n, found);
             if (rc) status = fail("gpuhash_first_below_batch", rc);
@@ -196,7 +256,7 @@ static int batch_main(const char *path, int below) {
                 if (found[k]) printf("Result %" PRIu64 " %" PRIu64 "\n", h[k], n[k]);
                 else printf("None\n");
             }
-            gpuhash_close(ctx);
+            close_ctx(ctx);
         } else {
             rc = gpuhash_min_batch(ctx, msgs, off, njobs, lower, upper, h, n);
             if (rc) status = fail("gpuhash_min_batch", rc);
@@ -208,7 +268,7 @@ static int batch_main(const char *path, int below) {
                 }
             }
             for (size_t k = 0; k < njobs && !status; k++) printf("Result %" PRIu64 " %" PRIu64 "\n", h[k], n[k]);
-            gpuhash_close(ctx);
+            close_ctx(ctx);
         }
     }
     free(h);
@@ -224,6 +284,18 @@ static int batch_main(const char *path, int below) {
 }
 
 int main(int argc, char **argv) {
+    struct sigaction sa;
+    memset(&sa, 0, sizeof sa);
+    sa.sa_handler = on_signal;
+    sigemptyset(&sa.sa_mask);
+    sigaction(SIGINT, &sa, NULL);
+    sigaction(SIGTERM, &sa, NULL);
+    if (argc >= 2 && strcmp(argv[1], "--progress") == 0) {
+        g_progress = 1;
+        argv[1] = argv[0];
+        argv++;
+        argc--;
+    }
     if (argc == 2 && strcmp(argv[1], "--version") == 0) {
         printf("%s\n", gpuhash_version());
         return 0;
@@ -248,13 +320,13 @@ int main(int argc, char **argv) {
         return 2;
     }
     gpuhash_ctx *ctx = NULL;
-    int rc = gpuhash_open(NULL, 0, &ctx);
+    int rc = open_ctx(&ctx);
     if (rc) return fail("gpuhash_open", rc);
     const size_t len = strlen(msg);
     int status = 0;
     if (range_mode) {
         uint64_t *out = (uint64_t *)malloc((size_t)(b ? b : 1) * sizeof(uint64_t));
-        if (!out) { gpuhash_close(ctx); return 3; }
+        if (!out) { close_ctx(ctx); return 3; }
         rc = gpuhash_hash_range(ctx, (const uint8_t *)msg, len, a, b, out);
         if (rc) status = fail("gpuhash_hash_range", rc);
         for (uint64_t i = 0; !rc && i < b; i++) printf("%" PRIu64 "\n", out[i]);
@@ -280,7 +352,7 @@ int main(int argc, char **argv) {
         uint64_t *nonces = (uint64_t *)malloc((room ? room : 1) * sizeof(uint64_t));
         uint64_t *hashes = (uint64_t *)malloc((room ? room : 1) * sizeof(uint64_t));
         uint64_t total = 0;
-        if (!nonces || !hashes) { free(nonces); free(hashes); gpuhash_close(ctx); return 3; }
+        if (!nonces || !hashes) { free(nonces); free(hashes); close_ctx(ctx); return 3; }
         rc = gpuhash_collect_below(ctx, (const uint8_t *)msg, len, a, b, target, nonces, hashes,
                                    cap > GPUHASH_COLLECT_MAX ? (size_t)GPUHASH_COLLECT_MAX + 1 : (size_t)cap, &total);
         if (rc) {
@@ -313,6 +385,6 @@ int main(int argc, char **argv) {
             printf("Result %" PRIu64 " %" PRIu64 "\n", h, n);
         }
     }
-    gpuhash_close(ctx);
+    close_ctx(ctx);
     return status;
 }

@@ -896,6 +896,15 @@ class Client {
         return conn_ != nullptr;
     }
 
+    // f runs once, on the client's own thread, when the connection is found lost: a program
+    // blocked in a long computation for the server learns of the loss there, not at its next
+    // read() (the miner cancels its search).  f must not call into this client.  Set it before
+    // the work starts; no message changes.
+    void on_lost(std::function<void()> f) {
+        std::lock_guard<std::mutex> lk(mu_);
+        on_lost_ = std::move(f);
+    }
+
     // The connection ID the server assigned (0 before the connection is up).
     long long conn_id() {
         std::lock_guard<std::mutex> lk(mu_);
@@ -949,6 +958,8 @@ class Client {
     CopyFilter copies_;
     std::unique_ptr<Conn> conn_;
     std::deque<std::string> reads_;
+    std::function<void()> on_lost_;
+    bool lost_told_ = false;
 
     void stop() {
         {
@@ -999,6 +1010,10 @@ class Client {
             return;
         }
         if (conn_->on_epoch()) cv_.notify_all();
+        if (conn_->lost() && !lost_told_) {
+            lost_told_ = true;
+            if (on_lost_) on_lost_();
+        }
     }
 };
 

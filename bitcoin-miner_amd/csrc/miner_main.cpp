@@ -22,7 +22,13 @@
 // hash the host re-computation disagrees with ends the miner, so every Request gets
 // exactly one Result or a lost connection, which the server requeues (an argument error
 // fails each miner the same way until the server's requeue cap disconnects the client).
+// A search nobody will read is not finished first: SIGTERM and SIGINT, and the LSP client's loss
+// of its connection (reported from the client's own thread), cancel the search in flight
+// (gpuhash_cancel), and the miner exits -- after a signal with status 128 + the signal, after a
+// loss as it always did when the server was lost.  The protocol is unchanged.
 // stdout is never written (the graders read it).
+#include <atomic>
+#include <csignal>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -34,6 +40,11 @@
 
 #include "gpuhash.h"
 #include "lsp_native.h"
+
+// The CPU tests link this program against the oracle's stand-in for the ABI (oracle/
+// gpuhash_oracle_abi.c), whose searches return at once and which has no gpuhash_cancel: the
+// reference is weak, and without it a signal or a lost server is handled as it was before.
+#pragma weak gpuhash_cancel
 
 namespace {
 
@@ -55,6 +66,25 @@ std::string result_json(uint64_t hash, uint64_t nonce) {  // json.Marshal(bitcoi
     r.hash = hash;
     r.nonce = nonce;
     return lspn::btc_marshal(r);
+}
+
+// What the signal handler and the client's loss hook reach: the context, whether a search is in
+// flight on it, and the signal that came.
+std::atomic<gpuhash_ctx*> g_ctx{nullptr};
+std::atomic<int> g_searching{0};
+volatile std::sig_atomic_t g_signal = 0;
+static_assert(std::atomic<gpuhash_ctx*>::is_always_lock_free && std::atomic<int>::is_always_lock_free,
+              "read in a signal handler");
+
+extern "C" void on_signal(int sig) {
+    gpuhash_ctx* const ctx = g_ctx.load();
+    if (gpuhash_cancel && ctx && g_searching.load()) {
+        g_signal = sig;
+        gpuhash_cancel(ctx);  // one atomic store: async-signal-safe; the main loop exits on it
+        return;
+    }
+    std::signal(sig, SIG_DFL);  // idle (blocked in read): end as before
+    std::raise(sig);
 }
 
 std::vector<int> devices_from_env() {
@@ -93,6 +123,12 @@ int main(int argc, char** argv) {
         logf("gpuhash_open: %s", gpuhash_strerror(rc));
         return 1;
     }
+    g_ctx.store(ctx);
+    client.on_lost([] {
+        if (gpuhash_cancel) gpuhash_cancel(g_ctx.load());
+    });  // nobody will read the job in flight
+    std::signal(SIGTERM, on_signal);
+    std::signal(SIGINT, on_signal);
     int status = 0;
     long long jobs = 0;
     logf("joined as connection %lld (pid %d)", client.conn_id(), (int)getpid());
@@ -109,8 +145,16 @@ int main(int argc, char** argv) {
             }
             // was: for n := m.Lower; n <= m.Upper; n++ { h := bitcoin.Hash(m.Data, n) ... }
             uint64_t h = 0, n = 0;
+            g_searching.store(1);
             rc = gpuhash_min(ctx, reinterpret_cast<const uint8_t*>(m.data.data()), m.data.size(), m.lower,
                              m.upper, &h, &n);
+            g_searching.store(0);
+            if (g_signal) {  // cancelled, or the signal came as the search ended: the server requeues the job
+                logf("job %s: signal %d; exiting", lspn::btc_describe(m).c_str(), (int)g_signal);
+                status = 128 + (int)g_signal;
+                break;
+            }
+            if (rc == GPUHASH_ECANCELED) break;  // the server is lost (reported below)
             // No Result can be sent for a failed job, and skipping it would leave it in
             // flight forever (the server pairs each Result with the miner's OLDEST job),
             // so every error ends the miner and the server requeues the job.
@@ -133,6 +177,10 @@ int main(int argc, char** argv) {
     }
     const std::string why = client.lost_reason();
     if (!why.empty()) logf("server lost after %lld job(s): %s", jobs, why.c_str());
+    std::signal(SIGTERM, SIG_DFL);
+    std::signal(SIGINT, SIG_DFL);
+    client.on_lost(nullptr);
+    g_ctx.store(nullptr);
     gpuhash_close(ctx);
     if (status == 0) client.close();  // flush the last Result; the server is gone otherwise
     return status;

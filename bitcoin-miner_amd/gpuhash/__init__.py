@@ -34,6 +34,7 @@ GPUHASH_ENODEV = -2
 GPUHASH_EHIP = -3
 GPUHASH_ETOOLONG = -4
 GPUHASH_ENOMEM = -5
+GPUHASH_ECANCELED = -6
 GPUHASH_MAX_MSG = 1 << 20
 GPUHASH_COLLECT_MAX = 1 << 20
 GPUHASH_BATCH_MAX_JOBS = 1 << 16
@@ -57,6 +58,7 @@ EXPORTED = [
     "gpuhash_first_below_batch", "gpuhash_first_below_batch_ex",
     "gpuhash_collect_below_batch", "gpuhash_collect_below_batch_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
+    "gpuhash_cancel", "gpuhash_resume", "gpuhash_progress",
     "gpuhash_close",
     "gpuhash_strerror", "gpuhash_version",
 ]
@@ -75,7 +77,7 @@ class GpuHashError(RuntimeError):
     @property
     def is_argument_error(self) -> bool:
         """True for EINVAL/ETOOLONG: retrying the job on another miner cannot succeed.
-        False for device/resource errors (ENODEV/EHIP/ENOMEM)."""
+        False for device/resource errors (ENODEV/EHIP/ENOMEM) and for ECANCELED."""
         return self.rc in ARGUMENT_ERRORS
 
 
@@ -199,6 +201,12 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
     lib.gpuhash_last_stats.restype = ctypes.c_int
     lib.gpuhash_last_launches.argtypes = [vp, ctypes.POINTER(LaunchRecord), ctypes.c_int]
     lib.gpuhash_last_launches.restype = ctypes.c_int
+    lib.gpuhash_cancel.argtypes = [vp]
+    lib.gpuhash_cancel.restype = ctypes.c_int
+    lib.gpuhash_resume.argtypes = [vp]
+    lib.gpuhash_resume.restype = ctypes.c_int
+    lib.gpuhash_progress.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.gpuhash_progress.restype = ctypes.c_int
     lib.gpuhash_close.argtypes = [vp]
     lib.gpuhash_close.restype = None
     lib.gpuhash_strerror.argtypes = [ctypes.c_int]
@@ -471,6 +479,30 @@ class Engine:
         arr = (LaunchRecord * max(n, 1))()
         n = self._lib.gpuhash_last_launches(self._ctx, arr, n)
         return [arr[i].as_dict() for i in range(n)]
+
+    def cancel(self) -> None:
+        """Stops the search in flight on this engine, from any thread, and every search after it
+        until resume(): they raise GpuHashError with rc == GPUHASH_ECANCELED (gpuhash_cancel: a
+        latch, one atomic store)."""
+        rc = self._lib.gpuhash_cancel(self._ctx)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_cancel")
+
+    def resume(self) -> None:
+        """Clears the cancel latch: searches started from now on run normally (gpuhash_resume)."""
+        rc = self._lib.gpuhash_resume(self._ctx)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_resume")
+
+    def progress(self) -> tuple[int, int]:
+        """(done, total) nonces of the search in flight, from any thread: total its nonce count,
+        done an estimate of those handed out to the device, which never decreases within a call;
+        (0, 0) with no search in flight (gpuhash_progress)."""
+        done, total = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self._lib.gpuhash_progress(self._ctx, ctypes.byref(done), ctypes.byref(total))
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_progress")
+        return int(done.value), int(total.value)
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):

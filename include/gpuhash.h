@@ -31,7 +31,8 @@
  * exception crosses the ABI (allocation failures map to GPUHASH_ENOMEM, any other
  * host-side failure, e.g. thread creation, to GPUHASH_EHIP).  GPUHASH_EINVAL and
  * GPUHASH_ETOOLONG are deterministic argument errors: retrying the same call elsewhere
- * fails the same way.  GPUHASH_ENODEV / EHIP / ENOMEM are device or resource errors.  The HIP
+ * fails the same way.  GPUHASH_ENODEV / EHIP / ENOMEM are device or resource errors, and
+ * GPUHASH_ECANCELED is neither: the caller asked for it (gpuhash_cancel).  The HIP
  * path is the only compute path: with no usable device gpuhash_open fails with
  * GPUHASH_ENODEV -- there is no silent CPU fallback.
  */
@@ -51,6 +52,7 @@ extern "C" {
 #define GPUHASH_EHIP (-3)     /* a HIP runtime call or kernel launch failed */
 #define GPUHASH_ETOOLONG (-4) /* msg_len > GPUHASH_MAX_MSG */
 #define GPUHASH_ENOMEM (-5)   /* device or host allocation failed */
+#define GPUHASH_ECANCELED (-6) /* the context's cancel latch is set (gpuhash_cancel) */
 
 /* The reference carries the message in a JSON frame inside <=2000-byte LSP datagrams
  * (lspnet/conn.go:35), so real messages are ~1.3 KB at most; the engine accepts more. */
@@ -171,7 +173,9 @@ int gpuhash_set_layout_policy(gpuhash_ctx *ctx, int policy);
  * Replaces the miner loop of p1.pdf pp.12-14 (miner.go:15) and feeds
  * bitcoin.NewResult(hash, nonce) (message.go:36-42).  msg is read during the call
  * only (cgo pointer rules); the range is split statically over the context's devices
- * (one host thread + one stream each), reduced on the host.  Blocking.  Any span is
+ * (one host thread + one stream each), reduced on the host.  Blocking, but not beyond reach:
+ * another thread, or a signal handler, ends the call with gpuhash_cancel and reads how far it
+ * is with gpuhash_progress (below).  Any span is
  * accepted, up to the full [0, 2^64-1]: spans over 2^38 nonces per device run as
  * consecutive slices (env GPUHASH_SLICE_NONCES overrides the per-device slice). */
 int gpuhash_min(gpuhash_ctx *ctx, const uint8_t *msg, size_t msg_len, uint64_t lower,
@@ -379,6 +383,52 @@ int gpuhash_last_stats(const gpuhash_ctx *ctx, gpuhash_stats *out);
 
 /* Copies up to cap launch records of the last call; returns how many exist. */
 int gpuhash_last_launches(const gpuhash_ctx *ctx, gpuhash_launch_record *out, int cap);
+
+/* Stops the search in flight on ctx, and every search after it until gpuhash_resume.
+ * Sets a LATCH on the context, not a one-shot signal: a cancel that arrives a microsecond before
+ * the call starts is not lost (Go's context.Context and C++ stop tokens behave the same way).
+ * May be called from any thread while another thread is inside any call on ctx; it takes no lock
+ * and does not wait.  It is ONE lock-free atomic store and nothing else, so it is
+ * async-signal-safe: gpuhash_cli and gpuhash_miner call it from their SIGINT / SIGTERM handlers.
+ * Returns GPUHASH_OK, or GPUHASH_EINVAL for a null ctx.
+ * While the latch is set every search entry point -- gpuhash_min, gpuhash_first_below,
+ * gpuhash_collect_below, their three batches, all their _ex forms and gpuhash_hash_range --
+ * returns GPUHASH_ECANCELED: the call in flight, promptly; callers queued on the context, when
+ * their turn comes; and calls made later.  A cancelled call writes NOTHING to its outputs and
+ * leaves gpuhash_last_stats / gpuhash_last_launches as any failed call leaves them.  Argument
+ * errors still win: GPUHASH_EINVAL / GPUHASH_ETOOLONG are returned before the latch is looked at.
+ * gpuhash_open, gpuhash_close, gpuhash_set_layout_policy, gpuhash_last_*, gpuhash_shard_range*
+ * and gpuhash_hash_cpu ignore the latch.
+ * How promptly: the thread that waits for the device polls the latch every 100 us (the default
+ * GPUHASH_HOST_WAIT=poll) and, when it sees it, overwrites the work counters of the launches in
+ * flight from a second stream, after which every resident workgroup finishes the piece it holds
+ * and leaves: milliseconds, whatever the range.  The latch is also read at call
+ * entry and before every slice, sub-batch and re-run.  Under GPUHASH_HOST_WAIT=stream or =event
+ * the waiting thread sleeps inside the HIP runtime, so there the latch is honoured at those
+ * launch boundaries ONLY: a cancel takes effect when the launches already enqueued have run.
+ * Replaces nothing in the reference; it is what a Go miner needs to honour a context.Context. */
+int gpuhash_cancel(gpuhash_ctx *ctx);
+
+/* Clears the latch.  A call that has already observed the latch still returns
+ * GPUHASH_ECANCELED; calls that start after gpuhash_resume returns run normally and are exact --
+ * nothing of a cancelled run (drained counters, half-filled lists, thresholds) reaches a later
+ * call: every call re-arms what it uses.  Any thread; no lock.  GPUHASH_EINVAL for a null ctx. */
+int gpuhash_resume(gpuhash_ctx *ctx);
+
+/* How far the search in flight on ctx is.  *out_total = the call's nonce count, saturating: the
+ * span; for a batch the sum of the spans; for gpuhash_first_below the span too (not the
+ * ascending-scan figure of gpuhash_last_stats).  *out_done = an estimate of the nonces whose work
+ * has been HANDED OUT to the device: the nonces of the slices, sub-batches and launches that are
+ * over, plus, for each launch now running, its nonces x the share of its work counter.  Within a
+ * call it never decreases and never exceeds *out_total; a first-hit search that stops early ends
+ * below it.  With no call in flight, or when the call ends before the answer is ready, both are 0.
+ * May be called from any thread; it takes no lock that a search holds, so it does not wait for
+ * the call as gpuhash_last_stats does.  The calling thread makes no HIP call: it posts a request,
+ * and the call's waiting threads answer it from their poll loop with one copy of the counters
+ * (about 0.1-0.3 ms).  A call nobody asks about enqueues nothing for it.  Under
+ * GPUHASH_HOST_WAIT=stream or =event the answer is what is over at launch boundaries, at once.
+ * Returns GPUHASH_OK, or GPUHASH_EINVAL for a null argument. */
+int gpuhash_progress(gpuhash_ctx *ctx, uint64_t *out_done, uint64_t *out_total);
 
 void gpuhash_close(gpuhash_ctx *ctx);
 

@@ -18,6 +18,7 @@ package gpuhash
 import "C"
 
 import (
+	"context"
 	"unsafe"
 )
 
@@ -84,6 +85,54 @@ func (e *Engine) Min(data string, lower, upper uint64) (hash, nonce uint64, err 
 	}
 	rc := C.gpuhash_min(e.ctx, nil, 0, C.uint64_t(lower), C.uint64_t(upper), &h, &n)
 	return uint64(h), uint64(n), rcErr(rc)
+}
+
+// Cancel stops the search in flight on the engine, from any goroutine, and every search after
+// it until Resume: they return an *Error with IsCancelled() true (gpuhash_cancel: a latch, one
+// atomic store, no lock).
+func (e *Engine) Cancel() error { return rcErr(C.gpuhash_cancel(e.ctx)) }
+
+// Resume clears the latch: searches started after it returns run normally.
+func (e *Engine) Resume() error { return rcErr(C.gpuhash_resume(e.ctx)) }
+
+// Progress reports how far the search in flight is: total its nonce count, done an estimate of
+// the nonces handed out to the device, which never decreases within a call; (0, 0) when no
+// search is in flight.  It does not wait for the search.
+func (e *Engine) Progress() (done, total uint64, err error) {
+	var d, t C.uint64_t
+	rc := C.gpuhash_progress(e.ctx, &d, &t)
+	return uint64(d), uint64(t), rcErr(rc)
+}
+
+// IsCancelled reports GPUHASH_ECANCELED: the search was stopped by Cancel, nothing failed.
+func (e *Error) IsCancelled() bool { return e.Code == int(C.GPUHASH_ECANCELED) }
+
+// MinContext is Min under a context.Context: when ctx is done the search in flight is
+// cancelled, within milliseconds, and ctx.Err() is returned.  The latch is cleared before
+// MinContext returns, so the engine is usable again.  One MinContext at a time per engine: the
+// latch belongs to the engine, not to the call.
+func (e *Engine) MinContext(ctx context.Context, data string, lower, upper uint64) (hash, nonce uint64, err error) {
+	if err := ctx.Err(); err != nil {
+		return 0, 0, err
+	}
+	finished := make(chan struct{})
+	watcher := make(chan struct{})
+	go func() {
+		defer close(watcher)
+		select {
+		case <-ctx.Done():
+			e.Cancel()
+		case <-finished:
+		}
+	}()
+	hash, nonce, err = e.Min(data, lower, upper)
+	close(finished)
+	<-watcher // no Cancel may follow the Resume
+	e.Resume()
+	if ge, ok := err.(*Error); ok && ge.IsCancelled() && ctx.Err() != nil {
+		return 0, 0, ctx.Err()
+	}
+	return hash, nonce, err
 }
 
 // FirstBelow returns the lowest nonce n of the inclusive [lower, upper] with
