@@ -377,6 +377,9 @@ struct ModeWiring {
     // job's answer of them.
     bool batch_collect;
 };
+// The packed group of a batch stage (stage.h, C2 = 4) is no mode of its own: k_pack reads the same
+// per-job words, list and list head as the scan kernels of the stage's mode, kScanBatch or
+// kScanCollectBatch, and everything after the launch is that mode's.
 constexpr ModeWiring kWiring[] = {
     /* kScanMin     */ {false, false, false, true},
     /* kScanDump    */ {false, false, false, false},
@@ -399,7 +402,7 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
     size_t sumgrid = 0;
     grids.reserve(ng);
     for (const StageGroup& g : st.groups) {
-        const unsigned int resident = grid_for(g.J, g.C2, g.EX, job.mode, d.ord);
+        const unsigned int resident = g.C2 == 4 ? pack_grid_for(job.mode, d.ord) : grid_for(g.J, g.C2, g.EX, job.mode, d.ord);
         if (resident == 0) return GPUHASH_EHIP;
         // a batch stage's list bound assumes at most kBatchMaxGrid workgroups (stage.h)
         grids.push_back(Stage::grid(g, st.njobs ? std::min<unsigned int>(resident, kBatchMaxGrid) : resident));
@@ -474,7 +477,13 @@ static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t 
         a.ktab = G.C2 == 3 ? reinterpret_cast<const uint32_t*>(d.d_meta + G.ptab_at) : d.d_ktab;
         a.grid = grids[g];
         HIPCHK(hipEventRecord(d.ev[2 * g], a.stream));
-        HIPCHK(launch_scan(G.J, G.C2, G.EX, job.mode, a));
+        if (G.C2 == 4) {  // the packed group: its tables instead of descriptors (pack.h)
+            const PackArgs p{d.stream, d.d_meta + st.pack_recs_at, d.d_meta + st.pack_segs_at, d.d_meta + st.pack_tiles_at,
+                             G.total, a.work, a.thresh, reinterpret_cast<BatchEntry*>(a.cands), a.ncand, a.grid};
+            HIPCHK(launch_pack(job.mode, p));
+        } else {
+            HIPCHK(launch_scan(G.J, G.C2, G.EX, job.mode, a));
+        }
         HIPCHK(hipEventRecord(d.ev[2 * g + 1], a.stream));
     }
     return GPUHASH_OK;
@@ -604,11 +613,11 @@ static int dev_run_batch(Dev& d, std::vector<PlannedJob>& jobs, size_t first, si
     d.used = true;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(d.ord));
-    std::vector<std::vector<Launch>> plans(end - first);
-    for (size_t k = first; k < end; k++) plans[k - first] = std::move(jobs[k].plan);
-    const Stage st = lists    ? Stage(plans, target + first, lists + first, buffer, rchunk)
+    StageJobs sj(jobs, first, end);
+    std::vector<std::vector<Launch>>& plans = sj.plans;
+    const Stage st = lists    ? Stage(plans, target + first, lists + first, buffer, rchunk, sj.which())
                      : target ? Stage(plans, target + first, rchunk)
-                              : Stage(plans, rchunk);
+                              : Stage(plans, rchunk, sj.which());
     const ScanJob job{lists ? kScanCollectBatch : target ? kScanFirstBatch : kScanBatch};
     std::vector<unsigned int> grids;
     int rc = stage_upload(d, st, job, grids);
@@ -757,8 +766,8 @@ int gpuhash_device_count(void) {
 static bool valid_policy(int policy) {
     const int base = policy & 15, flags = policy & ~15;
     return base >= GPUHASH_LAYOUT_AUTO && base <= GPUHASH_LAYOUT_LANETABLE &&
-           !(flags & ~(GPUHASH_LAYOUT_TAIL_ALWAYS | GPUHASH_LAYOUT_TAIL_NEVER)) &&
-           flags != (GPUHASH_LAYOUT_TAIL_ALWAYS | GPUHASH_LAYOUT_TAIL_NEVER);
+           !(flags & ~(GPUHASH_LAYOUT_TAIL_ALWAYS | GPUHASH_LAYOUT_TAIL_NEVER | GPUHASH_LAYOUT_PACKED_ALWAYS)) &&
+           (flags & ~GPUHASH_LAYOUT_PACKED_ALWAYS) != (GPUHASH_LAYOUT_TAIL_ALWAYS | GPUHASH_LAYOUT_TAIL_NEVER);
 }
 
 int gpuhash_shard_range(size_t msg_len, uint64_t lower, uint64_t upper, int nshards,
@@ -944,7 +953,8 @@ static int min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_of
     const int policy = ctx->policy;
     auto plan = [&](size_t k) {
         const size_t len = msg_off[k + 1] - msg_off[k];
-        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy);
+        const BatchJob j{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]};
+        return packs(policy, j.lo, j.hi) ? plan_packed_job(j) : plan_job(j, rchunk, policy);
     };
     auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
         const std::vector<std::pair<size_t, size_t>> runs = batch_runs(jobs, ctx->devs.size());
@@ -1126,8 +1136,9 @@ static int collect_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size
     auto plan = [&](size_t k) {
         size_t len;
         const uint8_t* const m = message(k, len);
-        return plan_job(BatchJob{m, len, lower[k], upper[k]}, rchunk, policy, /*host_ptab=*/false, /*pair=*/false,
-                        /*collects=*/true);
+        const BatchJob j{m, len, lower[k], upper[k]};
+        if (packs(policy, j.lo, j.hi)) return plan_packed_job(j, /*collects=*/true);
+        return plan_job(j, rchunk, policy, /*host_ptab=*/false, /*pair=*/false, /*collects=*/true);
     };
     auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
         const std::vector<std::pair<size_t, size_t>> runs = batch_runs(jobs, ctx->devs.size());

@@ -28,6 +28,9 @@
  *   gpuhash_cli --version
  * --progress in front of any of the searches prints "<done> <total>" (gpuhash_progress) on stderr
  * about once a second, from a second thread.
+ * --packed in front of --batch or --batch-all-below (after --progress, if both) sets
+ * GPUHASH_LAYOUT_PACKED_ALWAYS: jobs of at most GPUHASH_PACKED_MAX_SPAN nonces run packed, for
+ * files of tiny jobs.  The output is the same.
  * SIGINT and SIGTERM cancel the search in flight (gpuhash_cancel, from the handler): the run then
  * prints "Cancelled" on stderr, nothing on stdout, and exits 130.
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch, 130 cancelled.
@@ -48,6 +51,7 @@
 static gpuhash_ctx *volatile g_ctx;
 static volatile sig_atomic_t g_signalled;
 static int g_progress;
+static int g_packed;
 
 static void on_signal(int sig) {
     (void)sig;
@@ -77,6 +81,7 @@ static int open_ctx(gpuhash_ctx **out) {
     if (rc) return rc;
     g_ctx = *out;
     if (g_signalled) gpuhash_cancel(*out);
+    if (g_packed) gpuhash_set_layout_policy(*out, GPUHASH_LAYOUT_AUTO | GPUHASH_LAYOUT_PACKED_ALWAYS);
     if (g_progress && pthread_create(&g_progress_thread, NULL, progress_main, NULL) != 0) g_progress = 0;
     return rc;
 }
@@ -296,6 +301,12 @@ int main(int argc, char **argv) {
         argv++;
         argc--;
     }
+    if (argc >= 2 && strcmp(argv[1], "--packed") == 0) {
+        g_packed = 1;
+        argv[1] = argv[0];
+        argv++;
+        argc--;
+    }
     if (argc == 2 && strcmp(argv[1], "--version") == 0) {
         printf("%s\n", gpuhash_version());
         return 0;
@@ -308,7 +319,7 @@ int main(int argc, char **argv) {
     const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
     if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --all-below MSG LOWER UPPER TARGET [CAP] | --batch FILE | --batch-below FILE | --batch-all-below FILE | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | [--packed] --batch FILE | --batch-below FILE | [--packed] --batch-all-below FILE | --version\n", argv[0]);
         return 2;
     }
     const int opt = range_mode || below_mode || all_mode;

@@ -229,7 +229,10 @@ struct Staged {
     }
 
     // A batch stage: plans[k] = job k's plan, with host p-tables.
-    Staged(std::vector<std::vector<Launch>>& plans, uint32_t rchunk) : st(plans, rchunk), meta(st.bytes) {
+    // packed: the jobs of it that run packed (stage.h, StageJobs::which), or null.
+    Staged(std::vector<std::vector<Launch>>& plans, uint32_t rchunk,
+           const std::vector<const BatchJob*>* packed = nullptr)
+        : st(plans, rchunk, packed), meta(st.bytes) {
         read_groups();
     }
 
@@ -241,8 +244,8 @@ struct Staged {
 
     // A collect batch stage: as above, with lists[k] whether job k lists and the list's capacity.
     Staged(std::vector<std::vector<Launch>>& plans, const uint64_t* target, const uint8_t* lists,
-           uint64_t buffer_entries, uint32_t rchunk)
-        : st(plans, target, lists, buffer_entries, rchunk), meta(st.bytes) {
+           uint64_t buffer_entries, uint32_t rchunk, const std::vector<const BatchJob*>* packed = nullptr)
+        : st(plans, target, lists, buffer_entries, rchunk, packed), meta(st.bytes) {
         read_groups();
     }
 
@@ -651,6 +654,129 @@ struct BatchReplay {
     }
 };
 
+// ---- the packed group of a batch stage (pack.h): CPU replay of k_pack ----
+//
+// The group's tiles, segments and records from the bytes fill() wrote, and per lane pack.h's own
+// segment search, block building and compression -- never hash_host: the byte placement is what
+// the replay is for.  A wave's lanes are cut into runs of one job, as the kernel's ballot cuts
+// them, and a wave runs in two steps: it hashes and READS (the min mode's plain read of
+// thresh[job]), then does its atomics and stores.  Under a shuffle 2-8 workgroups are in flight,
+// each with ascending tiles and its waves in a random order, and the next step is any workgroup's:
+// other waves' atomics land between a wave's read and its own, and half the reads return the
+// stalest value there is, the word as armed.
+
+struct PackLane {
+    uint64_t h, n;
+};
+
+struct PackRun {
+    uint32_t job;
+    std::vector<PackLane> lanes;
+    uint64_t seen = ~0ull;
+};
+
+struct PackReplay {
+    const PackJob* recs;
+    const PackSeg* segs;
+    const PackTile* tiles;
+    uint64_t total;
+
+    explicit PackReplay(const Staged& r)
+        : recs(reinterpret_cast<const PackJob*>(r.meta.data() + r.st.pack_recs_at)),
+          segs(reinterpret_cast<const PackSeg*>(r.meta.data() + r.st.pack_segs_at)),
+          tiles(reinterpret_cast<const PackTile*>(r.meta.data() + r.st.pack_tiles_at)),
+          total(r.st.pack.tiles.size()) {}
+
+    std::vector<PackRun> wave(uint64_t x, uint32_t wv) const {
+        const PackTile& T = tiles[x];
+        std::vector<PackRun> runs;
+        for (uint32_t lane = 0; lane < 64; lane++) {
+            const uint64_t item = T.item0 + 64 * wv + lane;
+            const PackSeg& S = segs[pack_find_seg(segs, T.seg_first, T.seg_last, item)];
+            const uint64_t idx = item - S.start;
+            if (idx >= S.count) continue;  // idle: past the class's end
+            const PackJob& rec = recs[S.rec];
+            uint32_t H0, H1;
+            pack_hash(rec, T.o, T.d, S.n0 + idx, H0, H1);
+            if (runs.empty() || runs.back().job != rec.job) runs.push_back(PackRun{rec.job, {}});
+            runs.back().lanes.push_back(PackLane{(uint64_t)H0 << 32 | H1, S.n0 + idx});
+        }
+        return runs;
+    }
+
+    // order_seed 0: tiles and waves ascending; 1: descending; else the shuffle above.
+    template <class Read, class Commit>
+    void group(uint64_t order_seed, Rng& rng, Read&& read, Commit&& commit) const {
+        auto whole = [&](uint64_t x, uint32_t wv) {
+            std::vector<PackRun> runs = wave(x, wv);
+            for (PackRun& r : runs) read(r, false);
+            for (PackRun& r : runs) commit(r);
+        };
+        if (order_seed <= 1) {
+            for (uint64_t i = 0; i < total; i++)
+                for (uint32_t v = 0; v < 4; v++) order_seed ? whole(total - 1 - i, 3 - v) : whole(i, v);
+            return;
+        }
+        struct Wg {
+            std::vector<uint64_t> tiles;
+            size_t next = 0;
+            uint32_t done = 0, order[4] = {0, 1, 2, 3};
+            bool pending = false;
+            std::vector<PackRun> runs;
+        };
+        std::vector<Wg> wgs(2 + rng.next() % 7);
+        for (uint64_t x = 0; x < total; x++) wgs[rng.next() % wgs.size()].tiles.push_back(x);
+        std::vector<size_t> live;
+        for (size_t w = 0; w < wgs.size(); w++)
+            if (!wgs[w].tiles.empty()) live.push_back(w);
+        while (!live.empty()) {
+            const size_t at = rng.next() % live.size();
+            Wg& wg = wgs[live[at]];
+            if (!wg.pending) {
+                if (!wg.done)
+                    for (size_t i = 4; i > 1; i--) std::swap(wg.order[i - 1], wg.order[rng.next() % i]);
+                wg.runs = wave(wg.tiles[wg.next], wg.order[wg.done]);
+                for (PackRun& r : wg.runs) read(r, rng.next() % 2 == 0);
+                wg.pending = true;
+                continue;
+            }
+            for (PackRun& r : wg.runs) commit(r);
+            wg.pending = false;
+            if (++wg.done == 4) { wg.done = 0; wg.next++; }
+            if (wg.next == wg.tiles.size()) live.erase(live.begin() + (long)at);
+        }
+    }
+};
+
+// The min mode over the stage's pruning words and list, which `rep` holds for the unpacked groups
+// too.  The store is bounded by the capacity in the list's head; returns the appends it left out.
+uint64_t pack_min_group(const Staged& staged, BatchReplay& rep, uint64_t order_seed, Rng& rng) {
+    const PackReplay pk(staged);
+    uint32_t head[4];
+    std::memcpy(head, staged.meta.data() + staged.st.list_at, sizeof head);
+    const uint64_t cap = head[1];
+    uint64_t dropped = 0;
+    pk.group(order_seed, rng,
+             [&](PackRun& r, bool stale) {
+                 // the segmented minimum: the run's best by (hash, nonce) in its first lane
+                 PackLane b = r.lanes[0];
+                 for (const PackLane& l : r.lanes)
+                     if (l.h < b.h || (l.h == b.h && l.n < b.n)) b = l;
+                 r.lanes.assign(1, b);
+                 r.seen = stale ? ~0ull : rep.thresh[r.job];
+             },
+             [&](PackRun& r) {
+                 const PackLane& b = r.lanes[0];
+                 if (b.h > r.seen) return;
+                 const uint64_t old = rep.thresh[r.job];  // the atomicMin
+                 rep.thresh[r.job] = std::min(old, b.h);
+                 if (b.h > old) return;
+                 if (rep.list.size() + dropped < cap) rep.list.push_back(BatchEntry{b.h, b.n, r.job, 0});
+                 else dropped++;
+             });
+    return dropped;
+}
+
 }  // namespace
 
 extern "C" {
@@ -658,7 +784,9 @@ extern "C" {
 // gpuhash_min_batch as the engine runs it: the same sub-batches (for_each_sub_batch under
 // batch_bytes, 0: the engine's bound), runs over nshards context entries (batch_runs) and batch
 // stages, each run replayed as above with the order of its pieces chosen by order_seed (0, 1 or
-// a shuffle, see BatchReplay::group).  msg_off has njobs + 1 entries.  Returns 0 and the per-job
+// a shuffle, see BatchReplay::group).  Under a policy with GPUHASH_LAYOUT_PACKED_ALWAYS the jobs
+// that pack are staged and replayed as the packed group (PackReplay), whose appends count towards
+// the fill whether the bounded store kept them or not.  msg_off has njobs + 1 entries.  Returns 0 and the per-job
 // results, and in out_fill[0..3]: the largest result-list fill of any run, that run's bound
 // (Stage::list_cap), how many runs filled their list past its bound (0, or the bound is wrong),
 // and the number of sub-batches.
@@ -673,19 +801,24 @@ int hostcheck_min_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t n
     uint64_t fill[4] = {0, 0, 0, 0};
     auto plan = [&](size_t k) {
         const uint64_t len = msg_off[k + 1] - msg_off[k];
-        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy,
-                        /*host_ptab=*/true);
+        const BatchJob j{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]};
+        if (packs(policy, j.lo, j.hi)) return plan_packed_job(j);
+        return plan_job(j, rchunk, policy, /*host_ptab=*/true);
     };
     auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
         fill[3]++;
         for (const auto& r : batch_runs(jobs, (size_t)nshards)) {
-            std::vector<std::vector<Launch>> plans(r.second - r.first);
-            for (size_t k = r.first; k < r.second; k++) plans[k - r.first] = std::move(jobs[k].plan);
-            const Staged staged(plans, rchunk);
+            StageJobs sj(jobs, r.first, r.second);
+            const Staged staged(sj.plans, rchunk, sj.which());
             BatchReplay rep(staged);
-            for (size_t gi = 0; gi < staged.groups.size(); gi++) rep.group(gi, order_seed, rng);
-            if (rep.list.size() >= fill[0]) { fill[0] = rep.list.size(); fill[1] = staged.st.list_cap; }
-            fill[2] += rep.list.size() > staged.st.list_cap ? 1 : 0;
+            uint64_t dropped = 0;  // what the packed group's bounded store left out
+            for (size_t gi = 0; gi < staged.groups.size(); gi++) {
+                if (staged.st.groups[gi].C2 == 4) dropped += pack_min_group(staged, rep, order_seed, rng);
+                else rep.group(gi, order_seed, rng);
+            }
+            const uint64_t filled = rep.list.size() + dropped;
+            if (filled >= fill[0]) { fill[0] = filled; fill[1] = staged.st.list_cap; }
+            fill[2] += filled > staged.st.list_cap ? 1 : 0;
             for (size_t k = r.first; k < r.second; k++) out_hashes[first + k] = out_nonces[first + k] = ~0ull;
             for (const BatchEntry& e : rep.list) {  // the host's fold
                 uint64_t &h = out_hashes[first + r.first + e.job], &n = out_nonces[first + r.first + e.job];
@@ -700,7 +833,7 @@ int hostcheck_min_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t n
 }
 
 // The stage of ONE run of a batch (all njobs jobs on one context entry, no sub-batch cut) under
-// hostcheck_set_layout_policy's policy, as hostcheck_stage gives a single search's: the same 14
+// hostcheck_set_layout_policy's policy (with GPUHASH_LAYOUT_PACKED_ALWAYS: the packed group last), as hostcheck_stage gives a single search's: the same 14
 // words per variant group, *bytes and meta, and in extra[0..7] the bytes the host uploads, the
 // byte position and size of the per-job pruning words, the byte position of the result list
 // (its 16-byte head first) and its capacity in entries, the size of an entry, and the number
@@ -710,12 +843,17 @@ int hostcheck_stage_batch(const uint8_t* msgs, const uint64_t* msg_off, uint64_t
                           uint64_t* extra, uint8_t* meta, uint64_t meta_cap) {
     if (!msg_off || !lower || !upper || !bytes || !extra || !njobs) return -1;
     std::vector<std::vector<Launch>> plans(njobs);
+    std::vector<BatchJob> jobs(njobs);  // under GPUHASH_LAYOUT_PACKED_ALWAYS: the jobs that run packed
+    std::vector<const BatchJob*> packed(njobs, nullptr);
+    bool any = false;
     for (uint64_t k = 0; k < njobs; k++) {
         if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k]) return -1;
         const uint64_t len = msg_off[k + 1] - msg_off[k];
-        plan_range(len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k], plans[k], rchunk, g_policy);
+        jobs[k] = BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]};
+        if (packs(g_policy, lower[k], upper[k])) packed[k] = &jobs[k], any = true;
+        else plan_range(jobs[k].msg, len, lower[k], upper[k], plans[k], rchunk, g_policy);
     }
-    const Stage st(plans, rchunk);
+    const Stage st(plans, rchunk, any ? &packed : nullptr);
     for (int i = 0; i < (int)st.groups.size() && i < cap; i++) {
         const StageGroup& g = st.groups[(size_t)i];
         const uint64_t row[14] = {(uint64_t)g.J, (uint64_t)g.C2, (uint64_t)g.EX, g.idx.size(), (uint64_t)g.d,
@@ -1094,6 +1232,30 @@ struct CollectBatchReplay {
     }
 };
 
+// The packed group's collect mode over the stage's counters and list, which `rep` holds for the
+// unpacked groups too: per run one add on the job's counter and, if the job lists, one on the
+// list's append counter; the hits are stored in lane order while the slot is below the capacity.
+void pack_collect_group(const Staged& staged, CollectBatchReplay& rep, uint64_t order_seed, Rng& rng) {
+    const PackReplay pk(staged);
+    pk.group(order_seed, rng,
+             [&](PackRun& r, bool) {
+                 const uint64_t target = rep.words[kCollectJobWords * r.job + 1];
+                 std::vector<PackLane> hits;
+                 for (const PackLane& l : r.lanes)
+                     if (l.h <= target) hits.push_back(l);
+                 r.lanes.swap(hits);
+             },
+             [&](PackRun& r) {
+                 if (r.lanes.empty()) return;
+                 rep.counts[r.job] += r.lanes.size();
+                 if (!rep.words[kCollectJobWords * r.job + 2]) return;
+                 const uint64_t base = rep.appended;
+                 rep.appended += r.lanes.size();
+                 for (size_t i = 0; i < r.lanes.size(); i++)
+                     if (base + i < rep.cap) rep.list.push_back(BatchEntry{r.lanes[i].h, r.lanes[i].n, r.job, 0});
+             });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1103,7 +1265,9 @@ extern "C" {
 // batch stages and fold (collect.h, fold_collect_batch), each run replayed as above with the order
 // of its pieces chosen by order_seed (0, 1 or a shuffle) and a list of buffer_entries entries, and
 // each re-run replayed as hostcheck_collect_below replays a collection (one shard, the same list
-// size).  msg_off has njobs + 1 entries; out_off has njobs + 1 entries or is null (every cap 0).
+// size).  Under a policy with GPUHASH_LAYOUT_PACKED_ALWAYS the jobs that pack are staged and
+// replayed as the packed group (pack_collect_group); a re-run is unpacked, as in the engine.
+// msg_off has njobs + 1 entries; out_off has njobs + 1 entries or is null (every cap 0).
 // Returns 0 and out_totals[k], the lowest min(cap_k, total_k) hits of job k from out_off[k] on in
 // out_nonces / out_hashes (untouched beyond), and in out_info[0..3]: the largest number of entries
 // any run's list held, the number of jobs that were re-run, the number of sub-batches, and the
@@ -1135,8 +1299,9 @@ int hostcheck_collect_below_batch(const uint8_t* msgs, const uint64_t* msg_off, 
     auto plan = [&](size_t k) {
         uint64_t len;
         const uint8_t* const m = message(k, len);
-        return plan_job(BatchJob{m, len, lower[k], upper[k]}, rchunk, policy, /*host_ptab=*/true, /*pair=*/false,
-                        /*collects=*/true);
+        const BatchJob j{m, len, lower[k], upper[k]};
+        if (packs(policy, j.lo, j.hi)) return plan_packed_job(j, /*collects=*/true);
+        return plan_job(j, rchunk, policy, /*host_ptab=*/true, /*pair=*/false, /*collects=*/true);
     };
     auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
         info[2]++;
@@ -1144,11 +1309,13 @@ int hostcheck_collect_below_batch(const uint8_t* msgs, const uint64_t* msg_off, 
         for (size_t ri = 0; ri < runs.size(); ri++) {
             const auto& r = runs[ri];
             const size_t k0 = first + r.first, n = r.second - r.first;
-            std::vector<std::vector<Launch>> plans(n);
-            for (size_t k = r.first; k < r.second; k++) plans[k - r.first] = std::move(jobs[k].plan);
-            const Staged staged(plans, target + k0, lists.data() + k0, B, rchunk);
+            StageJobs sj(jobs, r.first, r.second);
+            const Staged staged(sj.plans, target + k0, lists.data() + k0, B, rchunk, sj.which());
             CollectBatchReplay rep(staged);
-            for (size_t gi = 0; gi < staged.groups.size(); gi++) rep.group(gi, order_seed, rng);
+            for (size_t gi = 0; gi < staged.groups.size(); gi++) {
+                if (staged.st.groups[gi].C2 == 4) pack_collect_group(staged, rep, order_seed, rng);
+                else rep.group(gi, order_seed, rng);
+            }
             info[0] = std::max<uint64_t>(info[0], rep.list.size());
             auto rerun = [&](size_t j, size_t cap, JobHits& out) {
                 const size_t k = k0 + j;

@@ -62,4 +62,23 @@ hipError_t launch_ktab(const LaunchDesc* d_desc, uint32_t* tab, uint32_t R, hipS
 hipError_t launch_ptab(const LaunchDesc* d_descs, int ndesc, uint32_t* tab, hipStream_t stream);
 hipError_t launch_reduce(Cand* cands, unsigned int* ncand, Cand* best, hipStream_t stream);
 
+// The packed group of a batch stage (stage.h, C2 = 4; pack_kernel.hip): one persistent launch of
+// k_pack over the group's tiles.  thresh, list and head are the batch stage's per-job words,
+// result list and list head, as kScanBatch / kScanCollectBatch wire them (gpuhash.cpp, kWiring).
+struct PackArgs {
+    hipStream_t stream;
+    const void* recs;                // device: the packed jobs' records (pack.h, PackJob)
+    const void* segs;                // device: the segments, by class (PackSeg)
+    const void* tiles;               // device: the tiles (PackTile)
+    unsigned long long ntiles;       // the group's total
+    unsigned long long* work;        // device: the group's counter block, as ScanArgs::work
+    unsigned long long* thresh;
+    BatchEntry* list;
+    unsigned int* head;
+    unsigned int grid;
+};
+// Resident workgroups of 256 threads of k_pack for the mode (kScanBatch or kScanCollectBatch).
+unsigned int pack_grid_for(int mode, int device);
+hipError_t launch_pack(int mode, const PackArgs& a);
+
 }  // namespace gpuhash

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "collect.h"
+#include "pack.h"
 #include "plan.h"
 
 namespace gpuhash {
@@ -104,6 +105,11 @@ inline uint64_t batch_job_entries(uint64_t span, uint32_t gmin, uint64_t grid) {
     return std::min<uint64_t>(grid, (span + gmin - 1) / gmin + 1);
 }
 
+// A PACKED job's entries are bounded per segment instead, with no grid or piece in the argument:
+// one entry at most per 64-item wave window of its class's space that the segment meets,
+// floor((c + 62) / 64) + 1 for c items (pack.h, pack_seg_entries, where the argument is stated);
+// Stage adds their sum, PackTables::entries, to list_cap.
+
 // The metadata bytes a job adds to a batch stage, at most (every alignment gap at its widest):
 // what the sub-batch cut (gpuhash.h) sums, with the K+W tables the job adds (BatchTables).
 // A first-hit batch (pair) has two words per job, and may put every launch in a group of its own:
@@ -147,11 +153,51 @@ struct BatchTables {
     }
 };
 
-// A job of a batch, planned: its launches, batch_job_bytes of them and their plan_cost.
+// A job of a batch, planned: its launches, batch_job_bytes of them and their plan_cost.  A packed
+// job (pack.h) has no launches: `src` is the job itself, for the stage's packed tables, `bytes` its
+// pack_job_bytes and `cost` its nonces at kPackCost.
 struct PlannedJob {
     std::vector<Launch> plan;
     uint64_t bytes;
     double cost;
+    bool packed = false;
+    BatchJob src{};
+};
+
+// Whether a job of gpuhash_min_batch or gpuhash_collect_below_batch runs packed under `policy`
+// (include/gpuhash.h, GPUHASH_LAYOUT_PACKED_ALWAYS).
+inline bool packs(int policy, uint64_t lo, uint64_t hi) {
+    return (policy & GPUHASH_LAYOUT_PACKED_ALWAYS) && hi - lo < kPackMaxSpan;
+}
+
+// A packed nonce against a nonce of a full row of the plain layouts (plan_cost's unit): it builds
+// its whole block and schedule itself.  Only the balance of a batch's runs over entries reads it.
+constexpr double kPackCost = 2.0;
+
+inline PlannedJob plan_packed_job(const BatchJob& j, bool collects = false) {
+    PlannedJob p;
+    p.bytes = pack_job_bytes(j.lo, j.hi, collects);
+    p.cost = kPackCost * (double)(j.hi - j.lo + 1);
+    p.packed = true;
+    p.src = j;
+    return p;
+}
+
+// The jobs [first, end) of a sub-batch as a batch stage takes them: their plans, moved from, and
+// which of them are packed (null when none is).
+struct StageJobs {
+    std::vector<std::vector<Launch>> plans;
+    std::vector<const BatchJob*> packed;
+    bool any = false;
+
+    StageJobs(std::vector<PlannedJob>& jobs, size_t first, size_t end) : plans(end - first), packed(end - first) {
+        for (size_t k = first; k < end; k++) {
+            plans[k - first] = std::move(jobs[k].plan);
+            packed[k - first] = jobs[k].packed ? &jobs[k].src : nullptr;
+            any = any || jobs[k].packed;
+        }
+    }
+    const std::vector<const BatchJob*>* which() const { return any ? &packed : nullptr; }
 };
 
 inline PlannedJob plan_job(const BatchJob& j, uint32_t rchunk, int policy, bool host_ptab = false,
@@ -257,6 +303,15 @@ struct Stage {
     // counters and re-runs them (collect.h, fold_collect_batch).
     bool collects = false;
     std::vector<uint8_t> lists;  // collects: one per job, cap_k > 0
+    // The packed jobs of a min or collect batch stage (pack.h; none unless the policy carries
+    // GPUHASH_LAYOUT_PACKED_ALWAYS): ONE more group, the last, {J = -1, C2 = 4, EX = 0}, without
+    // descriptors: its total is the tile count, its nonces the packed nonces, c the most tail
+    // blocks of any segment.  Its counter block sits with the other groups', and its tables --
+    // records, segments, tiles -- after the groups' regions and before the per-job region, inside
+    // the upload.  The per-job region and the list are shared by packed and unpacked jobs; the
+    // packed jobs add PackTables::entries to list_cap (pack.h, pack_seg_entries).
+    PackTables pack;
+    size_t pack_recs_at = 0, pack_segs_at = 0, pack_tiles_at = 0;
 
     Stage(const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi, uint32_t rchunk, int policy,
           bool host_ptab = false) : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)) {
@@ -267,13 +322,16 @@ struct Stage {
     // The stage of a batch: plans[k] is job k's plan_range under the context's policy (moved
     // from).  All launches of all jobs are grouped by (J, C2, EX) in first-appearance order;
     // within a group each job's descriptors are contiguous, jobs ascending.
-    Stage(std::vector<std::vector<Launch>>& plans, uint32_t rchunk)
+    // packed: null, or per job the job itself where it runs packed (its plan is then empty).
+    Stage(std::vector<std::vector<Launch>>& plans, uint32_t rchunk,
+          const std::vector<const BatchJob*>* packed = nullptr)
         : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()) {
         for (size_t k = 0; k < plans.size(); k++)
             for (Launch& l : plans[k]) {
                 l.desc.job = (uint32_t)k;
                 plan.push_back(std::move(l));
             }
+        if (packed) take_packed(*packed);
         lay_out();
     }
 
@@ -292,7 +350,7 @@ struct Stage {
     // The stage of a collect batch: plans[k] as above, target[k] job k's target, lists[k] whether
     // it lists, buffer_entries the capacity of the entry's list.  See collects.
     Stage(std::vector<std::vector<Launch>>& plans, const uint64_t* target, const uint8_t* lists_,
-          uint64_t buffer_entries, uint32_t rchunk)
+          uint64_t buffer_entries, uint32_t rchunk, const std::vector<const BatchJob*>* packed = nullptr)
         : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()),
           list_cap((size_t)std::min<uint64_t>(buffer_entries, 0xFFFFFFFFull)),
           targets(target, target + plans.size()), collects(true), lists(lists_, lists_ + plans.size()) {
@@ -301,6 +359,7 @@ struct Stage {
                 l.desc.job = (uint32_t)k;
                 plan.push_back(std::move(l));
             }
+        if (packed) take_packed(*packed);
         lay_out();
     }
 
@@ -310,6 +369,12 @@ struct Stage {
     size_t job_words_bytes() const { return collects ? 24 : by_digits ? 16 : 8; }
 
    private:
+    void take_packed(const std::vector<const BatchJob*>& packed) {
+        for (size_t k = 0; k < packed.size(); k++)
+            if (const BatchJob* j = packed[k]) pack.add_job((uint32_t)k, j->msg, j->len, j->lo, j->hi);
+        pack.finish();
+    }
+
     void lay_out() {
         for (size_t i = 0; i < plan.size(); i++) {
             const Launch& l = plan[i];
@@ -321,6 +386,12 @@ struct Stage {
                 it->d = l.d;
             }
             it->idx.push_back(i);
+        }
+        if (!pack.empty()) {
+            groups.push_back(StageGroup{-1, 4, 0});
+            groups.back().total = pack.tiles.size();
+            groups.back().nonces = pack.nonces;
+            groups.back().c = pack.blocks;
         }
         if (by_digits)
             std::stable_sort(groups.begin(), groups.end(),
@@ -370,6 +441,17 @@ struct Stage {
             bytes += g.ptab_bytes;
             align();
         }
+        if (!pack.empty()) {
+            pack_recs_at = bytes;
+            bytes += sizeof(PackJob) * pack.recs.size();
+            align();
+            pack_segs_at = bytes;
+            bytes += sizeof(PackSeg) * pack.segs.size();
+            align();
+            pack_tiles_at = bytes;
+            bytes += sizeof(PackTile) * pack.tiles.size();
+            align();
+        }
         upload_bytes = bytes;
         if (!njobs) return;
         thresh_at = bytes;
@@ -393,6 +475,7 @@ struct Stage {
                 }
             }
         }
+        list_cap += pack.entries;  // none without packed jobs
         bytes = list_at + kBatchListHead + sizeof(BatchEntry) * list_cap;
         align();
     }
@@ -413,6 +496,11 @@ struct Stage {
             }
             offs[g.idx.size()] = acc;
         }
+        if (!pack.empty()) {
+            std::memcpy(meta + pack_recs_at, pack.recs.data(), sizeof(PackJob) * pack.recs.size());
+            std::memcpy(meta + pack_segs_at, pack.segs.data(), sizeof(PackSeg) * pack.segs.size());
+            std::memcpy(meta + pack_tiles_at, pack.tiles.data(), sizeof(PackTile) * pack.tiles.size());
+        }
         if (collects) {
             for (size_t k = 0; k < njobs; k++) {  // {hit counter: 0, target, lists}
                 const uint64_t words[3] = {0ull, targets[k], lists[k] ? 1ull : 0ull};
@@ -431,7 +519,8 @@ struct Stage {
 
     // Workgroups of a group's launch, given the kernel's resident capacity on the device.
     static unsigned int grid(const StageGroup& g, unsigned int resident) {
-        const uint64_t pieces = (g.total + kMinPiece - 1) / kMinPiece;
+        // the packed group (C2 = 4) hands out tiles, down to one per grab (pack.h)
+        const uint64_t pieces = g.C2 == 4 ? g.total : (g.total + kMinPiece - 1) / kMinPiece;
         return (unsigned int)std::min<uint64_t>(resident, std::max<uint64_t>(pieces, 1));
     }
 };

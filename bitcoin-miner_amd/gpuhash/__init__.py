@@ -45,6 +45,8 @@ BATCH_COLLECT_CAP = 256
 LAYOUT_AUTO, LAYOUT_UNIFORM, LAYOUT_CLASSIC, LAYOUT_LANETABLE = 0, 1, 2, 3
 # OR-able flags: tail-digit launches always / never (include/gpuhash.h)
 LAYOUT_TAIL_ALWAYS, LAYOUT_TAIL_NEVER = 16, 32
+LAYOUT_PACKED_ALWAYS = 64  # min_batch and collect_below_batch: jobs of <= PACKED_MAX_SPAN nonces run packed
+PACKED_MAX_SPAN = 1 << 20
 TAIL_MIN_SPAN = 1 << 33
 
 # Every symbol include/gpuhash.h declares (tests check the .so exports all of them).
@@ -277,7 +279,9 @@ class Engine:
 
     def set_layout_policy(self, policy: int) -> None:
         """LAYOUT_AUTO / LAYOUT_UNIFORM / LAYOUT_CLASSIC / LAYOUT_LANETABLE, optionally OR
-        LAYOUT_TAIL_ALWAYS or LAYOUT_TAIL_NEVER (gpuhash_set_layout_policy)."""
+        LAYOUT_TAIL_ALWAYS or LAYOUT_TAIL_NEVER, and LAYOUT_PACKED_ALWAYS for batches of tiny
+        jobs: min_batch and collect_below_batch then pack every job of at most PACKED_MAX_SPAN
+        nonces, one (job, nonce) per GPU lane (gpuhash_set_layout_policy)."""
         rc = self._lib.gpuhash_set_layout_policy(self._ctx, policy)
         if rc != GPUHASH_OK:
             raise GpuHashError(rc, "gpuhash_set_layout_policy")

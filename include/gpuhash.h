@@ -167,6 +167,23 @@ int gpuhash_shard_range_policy(size_t msg_len, uint64_t lower, uint64_t upper, i
 #define GPUHASH_LAYOUT_TAIL_ALWAYS 16
 #define GPUHASH_LAYOUT_TAIL_NEVER 32
 #define GPUHASH_TAIL_MIN_SPAN 8589934592ull
+/* Packed tiny jobs, for any policy above, with or without a tail flag: OR
+ * GPUHASH_LAYOUT_PACKED_ALWAYS into the policy and every job of gpuhash_min_batch[_ex] and
+ * gpuhash_collect_below_batch[_ex] that has at most GPUHASH_PACKED_MAX_SPAN nonces is packed:
+ * it runs in one launch of a kernel whose every lane hashes one (job, nonce) from the job's
+ * midstate, so that no lane idles where the layouts above would fill a 256-lane row with a
+ * single nonce.  Larger jobs of the same call run exactly as without the flag, in the same
+ * stage.  Every other entry point accepts the flag and ignores it: the single calls
+ * (gpuhash_min, gpuhash_first_below, gpuhash_collect_below and their _ex forms),
+ * gpuhash_first_below_batch[_ex] (its value is its digit-ordered early exit, which packing
+ * would not help), gpuhash_hash_range and gpuhash_shard_range_policy.  Results are identical
+ * with and without the flag; only speed differs, and a packed nonce costs more instructions
+ * than a nonce of a full row: the flag is for hosts that know their jobs are tiny.  The cap is
+ * structural (at 10^6 nonces and more the layouts above fill their rows, and a packed job's
+ * index arithmetic stays within 32 bits), not a measured crossover: the flag forces packing up
+ * to it even where packing is slower. */
+#define GPUHASH_LAYOUT_PACKED_ALWAYS 64
+#define GPUHASH_PACKED_MAX_SPAN (1u << 20)
 int gpuhash_set_layout_policy(gpuhash_ctx *ctx, int policy);
 
 /* argmin_{n in [lower, upper]} (Hash(msg, n), n) -> *out_hash, *out_nonce.

@@ -9,7 +9,9 @@ code bytes, its register and segment figures, and a SHA-256 of its whole metadat
 tests/golden/kernel_manifest.txt is this tool's output for the product objects up to MODE 5, and
 tests/test_codegen.py holds the build against it; tests/golden/kernel_manifest_collect_batch.txt is
 its output for build/kernels_{plain,ut,misc}_collectbatch.o (MODE 6), held by
-tests/test_collect_below_batch_cpu.py.  The objects must exist (make builds them).
+tests/test_collect_below_batch_cpu.py; tests/golden/kernel_manifest_packed.txt is its output for
+build/pack.o (the packed kernel, which the default glob kernels*.o leaves out), held by
+tests/test_packed_cpu.py.  The objects must exist (make builds them).
 """
 import glob
 import hashlib
