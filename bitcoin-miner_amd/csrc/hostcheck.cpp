@@ -8,6 +8,7 @@
 // and never used to produce a search result.
 #include <algorithm>
 #include <cstring>
+#include <new>
 #include <numeric>
 #include <vector>
 
@@ -18,6 +19,43 @@
 using namespace gpuhash;
 
 static int g_policy = kLayoutAuto;
+
+// plan_range makes one Launch (about 700 bytes) per value of the leading digits H: a launch holds
+// at most 10^(s + q) <= 10^10 nonces (plan.h, kMaxLaunchDigits; a lane table's rectangle at most
+// 1024 * 10^8), so a whole 20-digit group is some 10^9 launches and the vector they are appended
+// to (plan_range's `out`) ends in std::bad_alloc.  The engine never plans such a range in one
+// piece (a search is cut into slices first); this library hands plans to ctypes, which an
+// exception must not reach.  The bound is a deliberate over-estimate of the launches of
+// [lower, upper] under any policy: it counts a launch per 10^min(d, 8) nonces of digit group d,
+// the least any layout gives a launch, where most layouts give 10^9 or 10^10.  So it also refuses
+// ranges whose plan would fit (2^48 nonces of the 15-digit group are about 28,000 launches, and
+// refused); no test plans one, and a refusal is a return code, not a wrong plan.
+constexpr uint64_t kMaxPlanLaunches = 1u << 18;
+constexpr int kPlanTooLarge = -2;  // refused by the estimate, or std::bad_alloc all the same
+constexpr int kPlanThrew = -3;     // any other exception: a fault of the planner, not of the range
+
+static bool plan_too_large(uint64_t lower, uint64_t upper) {
+    uint64_t est = 0;
+    for (int d = num_digits(lower); d <= num_digits(upper); d++) {
+        const uint64_t a = std::max(lower, d == 1 ? 0 : pow10u(d - 1));
+        const uint64_t b = std::min(upper, d == 20 ? UINT64_MAX : pow10u(d) - 1);
+        est += (b - a) / pow10u(std::min(d, 8)) + 32;
+    }
+    return est > kMaxPlanLaunches;
+}
+
+// f(), unless the plan is too large to hold; no exception leaves it.
+template <class F>
+static int guarded(uint64_t lower, uint64_t upper, F&& f) {
+    if (plan_too_large(lower, upper)) return kPlanTooLarge;
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return kPlanTooLarge;
+    } catch (...) {
+        return kPlanThrew;
+    }
+}
 
 extern "C" {
 
@@ -46,25 +84,32 @@ static gpuhash_plan_info plan_info(const Launch& l) {
 }
 
 int gpuhash_plan_count(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper, uint32_t rchunk) {
-    return lower > upper ? -1 : (int)plan_of(msg, len, lower, upper, rchunk).size();
+    if (lower > upper) return -1;
+    return guarded(lower, upper, [&] { return (int)plan_of(msg, len, lower, upper, rchunk).size(); });
 }
 
 int gpuhash_plan_get(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
                      uint32_t rchunk, int idx, gpuhash_plan_info* out) {
     if (lower > upper || !out) return -1;
-    const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
-    if (idx < 0 || idx >= (int)v.size()) return -1;
-    *out = plan_info(v[(size_t)idx]);
-    return 0;
+    return guarded(lower, upper, [&] {
+        const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
+        if (idx < 0 || idx >= (int)v.size()) return -1;
+        *out = plan_info(v[(size_t)idx]);
+        return 0;
+    });
 }
 
 // Whole plan in one call: fills up to cap entries, returns the launch count.
+// gpuhash_plan_count, _get and _all return -2 for a range whose plan is too large to hold, -3
+// should the planner throw anything but std::bad_alloc.
 int gpuhash_plan_all(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
                      uint32_t rchunk, gpuhash_plan_info* out, int cap) {
     if (lower > upper) return -1;
-    const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
-    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = plan_info(v[(size_t)i]);
-    return (int)v.size();
+    return guarded(lower, upper, [&] {
+        const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk);
+        for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = plan_info(v[(size_t)i]);
+        return (int)v.size();
+    });
 }
 
 int gpuhash_shard(uint64_t msg_len, uint64_t lower, uint64_t upper, int n, uint64_t* lo,
@@ -82,7 +127,13 @@ int gpuhash_shard(uint64_t msg_len, uint64_t lower, uint64_t upper, int n, uint6
 // The cost model's price of the plan of [lower, upper] (plan_cost): what a shard of that
 // range really costs under the layouts plan_range picks for it.
 double gpuhash_plan_cost(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper) {
-    return lower > upper ? -1 : plan_cost(plan_of(msg, len, lower, upper, 0));
+    if (lower > upper) return -1;
+    double cost = 0;
+    const int rc = guarded(lower, upper, [&] {
+        cost = plan_cost(plan_of(msg, len, lower, upper, 0));
+        return 0;
+    });
+    return rc ? (double)rc : cost;
 }
 
 }  // extern "C"
@@ -158,9 +209,12 @@ static uint64_t replay_hash(const Launch& l, uint32_t p, uint32_t r) {
 
 extern "C" {
 
-// Replays the kernel's per-nonce computation from launch `idx`'s descriptor.
-int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
-                        uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
+// Replays the kernel's per-nonce computation from launch `idx`'s descriptor.  Returns 0, -1 for
+// a bad range or index, -2 for a nonce outside the launch, -3 for one outside a lane table's
+// rectangle, -4 for a range whose plan is too large to hold (as the plan entry points' -2) and
+// -5 should the planner or the replay throw anything else: no exception leaves it.
+static int desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                     uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
     const std::vector<Launch> v = plan_of(msg, len, lower, upper, rchunk, /*host_ptab=*/true);
     if (idx < 0 || idx >= (int)v.size()) return -1;
     const Launch& l = v[(size_t)idx];
@@ -180,6 +234,19 @@ int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64
     const uint64_t off = nonce / D.stride - D.base;
     *out = replay_hash(l, (uint32_t)(off / D.R), (uint32_t)(off % D.R));
     return 0;
+}
+
+int hostcheck_desc_hash(const uint8_t* msg, uint64_t len, uint64_t lower, uint64_t upper,
+                        uint32_t rchunk, int idx, uint64_t nonce, uint64_t* out) {
+    if (lower > upper || !out) return -1;
+    if (plan_too_large(lower, upper)) return -4;
+    try {
+        return desc_hash(msg, len, lower, upper, rchunk, idx, nonce, out);
+    } catch (const std::bad_alloc&) {
+        return -4;
+    } catch (...) {
+        return -5;
+    }
 }
 
 }  // extern "C"
