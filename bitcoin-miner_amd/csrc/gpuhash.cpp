@@ -379,7 +379,8 @@ struct ModeWiring {
 };
 // The packed group of a batch stage (stage.h, C2 = 4) is no mode of its own: k_pack reads the same
 // per-job words, list and list head as the scan kernels of the stage's mode, kScanBatch or
-// kScanCollectBatch, and everything after the launch is that mode's.
+// kScanCollectBatch, and everything after the launch is that mode's.  Likewise k_pack_first under
+// kScanFirstBatch (a round of gpuhash_first_below_batch_early).
 constexpr ModeWiring kWiring[] = {
     /* kScanMin     */ {false, false, false, true},
     /* kScanDump    */ {false, false, false, false},
@@ -402,7 +403,9 @@ static int stage_upload(Dev& d, const Stage& st, const ScanJob& job, std::vector
     size_t sumgrid = 0;
     grids.reserve(ng);
     for (const StageGroup& g : st.groups) {
-        const unsigned int resident = g.C2 == 4 ? pack_grid_for(job.mode, d.ord) : grid_for(g.J, g.C2, g.EX, job.mode, d.ord);
+        const unsigned int resident = g.C2 != 4                      ? grid_for(g.J, g.C2, g.EX, job.mode, d.ord)
+                                      : job.mode == kScanFirstBatch ? pack_first_grid_for(d.ord)
+                                                                    : pack_grid_for(job.mode, d.ord);
         if (resident == 0) return GPUHASH_EHIP;
         // a batch stage's list bound assumes at most kBatchMaxGrid workgroups (stage.h)
         grids.push_back(Stage::grid(g, st.njobs ? std::min<unsigned int>(resident, kBatchMaxGrid) : resident));
@@ -480,7 +483,8 @@ static int arm_and_launch(Dev& d, const Stage& st, const ScanJob& job, uint64_t 
         if (G.C2 == 4) {  // the packed group: its tables instead of descriptors (pack.h)
             const PackArgs p{d.stream, d.d_meta + st.pack_recs_at, d.d_meta + st.pack_segs_at, d.d_meta + st.pack_tiles_at,
                              G.total, a.work, a.thresh, reinterpret_cast<BatchEntry*>(a.cands), a.ncand, a.grid};
-            HIPCHK(launch_pack(job.mode, p));
+            // a first-hit batch stage's packed group is a round of gpuhash_first_below_batch_early
+            HIPCHK(job.mode == kScanFirstBatch ? launch_pack_first(p) : launch_pack(job.mode, p));
         } else {
             HIPCHK(launch_scan(G.J, G.C2, G.EX, job.mode, a));
         }
@@ -521,7 +525,7 @@ static int read_back(Dev& d, const Stage& st, const ScanJob& job, uint64_t lo, u
         d.recs.push_back(gpuhash_launch_record{d.ord, G.J, G.C2, G.EX, G.d, G.c, d.shard, d.stream_dev, lo, hi,
                                                G.nonces, (double)ms, sclk});
     }
-    d.launches = (uint32_t)st.groups.size();
+    d.launches += (uint32_t)st.groups.size();  // an entry may run several stages between two resets
     return GPUHASH_OK;
 }
 
@@ -606,23 +610,26 @@ static int dev_run(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
 // into the stage; index0 is the batch index of jobs[0], for the launch records.
 // target: null for gpuhash_min_batch, else the targets of jobs[0..) for gpuhash_first_below_batch
 // and, with lists (whether each of jobs[0..) lists) and the entry's list capacity `buffer`, for
-// gpuhash_collect_below_batch.
+// gpuhash_collect_below_batch.  index_of: null, or the batch index of every position index0 + k
+// where the jobs are a selection of the batch's (gpuhash_first_below_batch_early): the launch
+// records then carry the batch indices of the run's first and last job.
 static int dev_run_batch(Dev& d, std::vector<PlannedJob>& jobs, size_t first, size_t end, size_t index0,
                          uint32_t rchunk, const uint64_t* target = nullptr, const uint8_t* lists = nullptr,
-                         uint64_t buffer = 0) {
+                         uint64_t buffer = 0, const size_t* index_of = nullptr) {
     d.used = true;
     DeviceGuard guard;
     HIPCHK(hipSetDevice(d.ord));
     StageJobs sj(jobs, first, end);
     std::vector<std::vector<Launch>>& plans = sj.plans;
     const Stage st = lists    ? Stage(plans, target + first, lists + first, buffer, rchunk, sj.which())
-                     : target ? Stage(plans, target + first, rchunk)
+                     : target ? Stage(plans, target + first, rchunk, sj.which())
                               : Stage(plans, rchunk, sj.which());
     const ScanJob job{lists ? kScanCollectBatch : target ? kScanFirstBatch : kScanBatch};
     std::vector<unsigned int> grids;
     int rc = stage_upload(d, st, job, grids);
     if (!rc) rc = arm_and_launch(d, st, job, 0, grids);
-    if (!rc) rc = read_back(d, st, job, index0 + first, index0 + end - 1);
+    const size_t lo = index0 + first, hi = index0 + end - 1;
+    if (!rc) rc = read_back(d, st, job, index_of ? index_of[lo] : lo, index_of ? index_of[hi] : hi);
     return rc ? rc : decode(d, job, st);
 }
 
@@ -1005,20 +1012,19 @@ int gpuhash_min_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_o
     return gpuhash_min_batch_ex(ctx, msgs, msg_off, njobs, lower, upper, 0, out_hashes, out_nonces);
 }
 
-// gpuhash_first_below_batch_ex, its arguments checked: min_batch's sub-batches and runs, each run
-// one first-hit batch stage (stage.h, Stage::by_digits) and one launch per group of it.
-static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
-                             const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
-                             uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    Call call(ctx, spans_of(njobs, lower, upper));
-    if (call.cancelled()) return GPUHASH_ECANCELED;
-    std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
-    std::vector<uint8_t> rf(njobs);
+// The body gpuhash_first_below_batch_ex and the remainder of gpuhash_first_below_batch_early
+// share: the first-hit searches of n jobs over [lower[i], upper[i]] with target[i], as min_batch's
+// sub-batches and runs, each run one first-hit batch stage (stage.h, Stage::by_digits) and one
+// launch per group of it.  Job i is job sel[i] of the call's batch (sel null: job i), which names
+// its message and, in the launch records, its index.  rh, rn and rf take the results, by i.
+static int first_batch_runs(Call& call, const uint8_t* msgs, const size_t* msg_off, const size_t* sel, size_t n,
+                            const uint64_t* lower, const uint64_t* upper, const uint64_t* target, uint32_t rchunk,
+                            uint64_t* rh, uint64_t* rn, uint8_t* rf) {
+    gpuhash_ctx* const ctx = call.ctx;
     const int policy = ctx->policy;
-    auto plan = [&](size_t k) {
-        const size_t len = msg_off[k + 1] - msg_off[k];
-        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[k], upper[k]}, rchunk, policy,
+    auto plan = [&](size_t i) {
+        const size_t k = sel ? sel[i] : i, len = msg_off[k + 1] - msg_off[k];
+        return plan_job(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lower[i], upper[i]}, rchunk, policy,
                         /*host_ptab=*/false, /*pair=*/true);
     };
     auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
@@ -1026,7 +1032,8 @@ static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t
         const int rc = call.run_each(runs.size(), [&](size_t r) {
             Dev& d = ctx->devs[r];
             d.rc = guarded([&] {
-                return dev_run_batch(d, jobs, runs[r].first, runs[r].second, first, rchunk, target + first);
+                return dev_run_batch(d, jobs, runs[r].first, runs[r].second, first, rchunk, target + first, nullptr, 0,
+                                     sel);
             });
         });
         if (rc) return rc;
@@ -1040,8 +1047,16 @@ static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t
         }
         return GPUHASH_OK;
     };
-    if (int rc = for_each_sub_batch(njobs, batch_bytes_bound(), plan, run)) return rc;
-    uint64_t nonces = 0;  // what an ascending scan of every job would have examined
+    return for_each_sub_batch(n, batch_bytes_bound(), plan, run);
+}
+
+// What an ascending scan of every job would have examined (gpuhash_last_stats().nonces of the
+// first-hit batches), then the outputs: a job that is not found leaves its two untouched.
+static void first_batch_finish(Call& call, size_t njobs, const uint64_t* lower, const uint64_t* upper,
+                               const std::vector<uint64_t>& rh, const std::vector<uint64_t>& rn,
+                               const std::vector<uint8_t>& rf, uint64_t* out_hashes, uint64_t* out_nonces,
+                               int* out_found) {
+    uint64_t nonces = 0;
     for (size_t k = 0; k < njobs; k++) {
         const uint64_t n = (rf[k] ? rn[k] : upper[k]) - lower[k] + 1;  // <= GPUHASH_BATCH_MAX_SPAN
         nonces = nonces + n < nonces ? ~0ull : nonces + n;
@@ -1053,12 +1068,145 @@ static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t
         out_hashes[k] = rh[k];
         out_nonces[k] = rn[k];
     }
+}
+
+// gpuhash_first_below_batch_ex, its arguments checked.
+static int first_below_batch(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                             const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                             uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Call call(ctx, spans_of(njobs, lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
+    std::vector<uint64_t> rh(njobs), rn(njobs);  // the outputs are written only when all ran
+    std::vector<uint8_t> rf(njobs);
+    if (int rc = first_batch_runs(call, msgs, msg_off, nullptr, njobs, lower, upper, target, rchunk, rh.data(),
+                                  rn.data(), rf.data()))
+        return rc;
+    first_batch_finish(call, njobs, lower, upper, rh, rn, rf, out_hashes, out_nonces, out_found);
     return GPUHASH_OK;
 }
 
-int gpuhash_first_below_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
-                                 const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
-                                 uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+// One context entry's packed phase of gpuhash_first_below_batch_early: the jobs `mine` (batch
+// indices, ascending), which it alone reads and writes, in ascending rounds of doubling pieces
+// (include/gpuhash.h).  A round is one first-hit batch stage per sub-batch that holds the packed
+// group and nothing else; a job with an entry is answered by its lowest nonce and closed, every
+// other job's front advances by its piece.  used[k] counts the nonces of job k handed out so far.
+struct EarlyJobs {
+    const uint8_t* msgs;
+    const size_t* msg_off;
+    const uint64_t *lower, *target;
+    const uint64_t* limit;
+    const PackJob* recs;  // by batch index: built once per call
+    uint64_t *used, *rh, *rn;
+    uint8_t* rf;
+};
+
+static int early_rounds(Dev& d, const EarlyJobs& J, const std::vector<size_t>& mine, uint64_t c0, uint32_t rchunk) {
+    const uint64_t bound = batch_bytes_bound();
+    std::vector<size_t> open;
+    std::vector<BatchJob> piece;
+    std::vector<uint64_t> tg;
+    for (uint64_t c = c0;; c = early_next_chunk(c)) {
+        open.clear();
+        piece.clear();
+        tg.clear();
+        for (size_t k : mine) {
+            if (J.rf[k] || J.used[k] >= J.limit[k]) continue;
+            const uint64_t lo = J.lower[k] + J.used[k], len = J.msg_off[k + 1] - J.msg_off[k];
+            open.push_back(k);
+            piece.push_back(BatchJob{len ? J.msgs + J.msg_off[k] : nullptr, len, lo,
+                                     lo + (std::min(c, J.limit[k] - J.used[k]) - 1), J.recs + k});
+            tg.push_back(J.target[k]);
+        }
+        if (open.empty()) return GPUHASH_OK;
+        auto plan = [&](size_t i) {
+            PlannedJob p = plan_packed_job(piece[i]);
+            p.bytes += 8;  // its per-job words are a pair
+            return p;
+        };
+        auto run = [&](size_t first, std::vector<PlannedJob>& jobs) -> int {
+            if (d.ctl->observe()) return GPUHASH_ECANCELED;  // before every round and every sub-batch
+            if (int rc = dev_run_batch(d, jobs, 0, jobs.size(), first, rchunk, tg.data() + first, nullptr, 0, open.data()))
+                return rc;
+            for (size_t i = 0; i < jobs.size(); i++) {
+                const size_t k = open[first + i];
+                if (!d.bat_found[i]) continue;
+                J.rf[k] = 1;
+                J.rh[k] = d.bat_h[i];
+                J.rn[k] = d.bat_n[i];
+            }
+            return GPUHASH_OK;
+        };
+        if (int rc = for_each_sub_batch(open.size(), bound, plan, run)) return rc;
+        for (size_t i = 0; i < open.size(); i++) J.used[open[i]] += piece[i].hi - piece[i].lo + 1;
+    }
+}
+
+// gpuhash_first_below_batch_early, its arguments checked: the packed rounds of every job's front,
+// each context entry over a contiguous run of the jobs that have one, then first_batch_runs over
+// what is left of the jobs still open.
+static int first_below_batch_early(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                   const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                   uint64_t prefix, uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces,
+                                   int* out_found) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    Call call(ctx, spans_of(njobs, lower, upper));
+    if (call.cancelled()) return GPUHASH_ECANCELED;
+    std::vector<uint64_t> rh(njobs), rn(njobs), limit(njobs), used(njobs, 0);
+    std::vector<uint8_t> rf(njobs);
+    std::vector<size_t> fronts;
+    for (size_t k = 0; k < njobs; k++) {
+        limit[k] = early_limit(lower[k], upper[k], target[k], prefix);
+        if (limit[k]) fronts.push_back(k);
+    }
+    if (!fronts.empty()) {
+        std::vector<PackJob> recs(njobs);
+        for (size_t k : fronts) {
+            const size_t len = msg_off[k + 1] - msg_off[k];
+            recs[k] = PackTables::record(len ? msgs + msg_off[k] : nullptr, len);
+        }
+        const EarlyJobs J{msgs, msg_off, lower, target, limit.data(), recs.data(), used.data(), rh.data(), rn.data(), rf.data()};
+        const uint64_t c0 = early_first_chunk(fronts.size());
+        const size_t nruns = std::min(ctx->devs.size(), fronts.size());
+        std::vector<std::vector<size_t>> mine(nruns);
+        for (size_t r = 0; r < nruns; r++)
+            mine[r].assign(fronts.begin() + (long)(fronts.size() * r / nruns),
+                           fronts.begin() + (long)(fronts.size() * (r + 1) / nruns));
+        const int rc = call.run_each(nruns, [&](size_t r) {
+            Dev& d = ctx->devs[r];
+            d.rc = guarded([&] { return early_rounds(d, J, mine[r], c0, rchunk); });
+        });
+        if (rc) return rc;
+    }
+    std::vector<size_t> sel;
+    std::vector<uint64_t> lo2, hi2, tg2;
+    for (size_t k = 0; k < njobs; k++) {
+        if (rf[k] || used[k] > upper[k] - lower[k]) continue;  // answered, or its front was all of it
+        sel.push_back(k);
+        lo2.push_back(lower[k] + used[k]);
+        hi2.push_back(upper[k]);
+        tg2.push_back(target[k]);
+    }
+    if (!sel.empty()) {
+        std::vector<uint64_t> h2(sel.size()), n2(sel.size());
+        std::vector<uint8_t> f2(sel.size());
+        if (int rc = first_batch_runs(call, msgs, msg_off, sel.data(), sel.size(), lo2.data(), hi2.data(), tg2.data(),
+                                      rchunk, h2.data(), n2.data(), f2.data()))
+            return rc;
+        for (size_t i = 0; i < sel.size(); i++) {
+            rf[sel[i]] = f2[i];
+            rh[sel[i]] = h2[i];
+            rn[sel[i]] = n2[i];
+        }
+    }
+    first_batch_finish(call, njobs, lower, upper, rh, rn, rf, out_hashes, out_nonces, out_found);
+    return GPUHASH_OK;
+}
+
+// The whole-call argument errors of the first-hit batches: 0, or the error.
+static int first_batch_args(const gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                            const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                            const uint64_t* out_hashes, const uint64_t* out_nonces, const int* out_found) {
     if (!ctx || !msg_off || !lower || !upper || !target || !out_hashes || !out_nonces || !out_found)
         return GPUHASH_EINVAL;
     if (njobs == 0 || njobs > GPUHASH_BATCH_MAX_JOBS) return GPUHASH_EINVAL;
@@ -1069,10 +1217,30 @@ int gpuhash_first_below_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const si
         too_long = too_long || msg_off[k + 1] - msg_off[k] > GPUHASH_MAX_MSG;
     }
     if (!msgs && msg_off[njobs] != msg_off[0]) return GPUHASH_EINVAL;
-    if (too_long) return GPUHASH_ETOOLONG;
+    return too_long ? GPUHASH_ETOOLONG : GPUHASH_OK;
+}
+
+int gpuhash_first_below_batch_ex(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                 const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                 uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces, int* out_found) {
+    if (int rc = first_batch_args(ctx, msgs, msg_off, njobs, lower, upper, target, out_hashes, out_nonces, out_found))
+        return rc;
     return guarded([&] {
         return first_below_batch(ctx, msgs, msg_off, njobs, lower, upper, target, rchunk, out_hashes, out_nonces,
                                  out_found);
+    });
+}
+
+int gpuhash_first_below_batch_early(gpuhash_ctx* ctx, const uint8_t* msgs, const size_t* msg_off, size_t njobs,
+                                    const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                    uint64_t prefix, uint32_t rchunk, uint64_t* out_hashes, uint64_t* out_nonces,
+                                    int* out_found) {
+    if (prefix > GPUHASH_BATCH_MAX_SPAN) return GPUHASH_EINVAL;
+    if (int rc = first_batch_args(ctx, msgs, msg_off, njobs, lower, upper, target, out_hashes, out_nonces, out_found))
+        return rc;
+    return guarded([&] {
+        return first_below_batch_early(ctx, msgs, msg_off, njobs, lower, upper, target, prefix, rchunk, out_hashes,
+                                       out_nonces, out_found);
     });
 }
 
@@ -1311,9 +1479,9 @@ const char* gpuhash_strerror(int rc) {
 
 const char* gpuhash_version(void) {
 #ifdef GPUHASH_TIE_TEST_BITS
-    return "gpuhash 0.8 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
+    return "gpuhash 0.9 gfx950 build=" GPUHASH_BUILD_ID " TIE-TEST (truncated keys; test build only)";
 #else
-    return "gpuhash 0.8 gfx950 build=" GPUHASH_BUILD_ID;
+    return "gpuhash 0.9 gfx950 build=" GPUHASH_BUILD_ID;
 #endif
 }
 

@@ -31,6 +31,9 @@
  * --packed in front of --batch or --batch-all-below (after --progress, if both) sets
  * GPUHASH_LAYOUT_PACKED_ALWAYS: jobs of at most GPUHASH_PACKED_MAX_SPAN nonces run packed, for
  * files of tiny jobs.  The output is the same.
+ * --early in front of --batch-below (after --progress) makes that one call
+ * gpuhash_first_below_batch_early, for files of stamp jobs whose first hit lies early in a long
+ * range: the front of every job runs packed, in doubling rounds.  The output is the same.
  * SIGINT and SIGTERM cancel the search in flight (gpuhash_cancel, from the handler): the run then
  * prints "Cancelled" on stderr, nothing on stdout, and exits 130.
  * Exit status: 0 ok, 2 usage, 3 library error (message on stderr), 4 self-check mismatch, 130 cancelled.
@@ -52,6 +55,7 @@ static gpuhash_ctx *volatile g_ctx;
 static volatile sig_atomic_t g_signalled;
 static int g_progress;
 static int g_packed;
+static int g_early;
 
 static void on_signal(int sig) {
     (void)sig;
@@ -247,8 +251,9 @@ static int batch_main(const char *path, int below) {
             status = batch_all_main(ctx, msgs, off, njobs, lower, upper, target, caps);
             close_ctx(ctx);
         } else if (below) {
-            rc = gpuhash_first_below_batch(ctx, msgs, off, njobs, lower, upper, target, h, n, found);
-            if (rc) status = fail("gpuhash_first_below_batch", rc);
+            rc = g_early ? gpuhash_first_below_batch_early(ctx, msgs, off, njobs, lower, upper, target, 0, 0, h, n, found)
+                         : gpuhash_first_below_batch(ctx, msgs, off, njobs, lower, upper, target, h, n, found);
+            if (rc) status = fail(g_early ? "gpuhash_first_below_batch_early" : "gpuhash_first_below_batch", rc);
             for (size_t k = 0; k < njobs && !status; k++) { /* --below's self-check, per found job */
                 if (found[k] && (gpuhash_hash_cpu(msgs + off[k], off[k + 1] - off[k], n[k]) != h[k] || h[k] > target[k] ||
                                  n[k] < lower[k] || n[k] > upper[k])) {
@@ -307,6 +312,12 @@ int main(int argc, char **argv) {
         argv++;
         argc--;
     }
+    if (argc == 4 && strcmp(argv[1], "--early") == 0 && strcmp(argv[2], "--batch-below") == 0) {
+        g_early = 1;
+        argv[1] = argv[0];
+        argv++;
+        argc--;
+    }
     if (argc == 2 && strcmp(argv[1], "--version") == 0) {
         printf("%s\n", gpuhash_version());
         return 0;
@@ -319,7 +330,7 @@ int main(int argc, char **argv) {
     const int all_mode = (argc == 6 || argc == 7) && strcmp(argv[1], "--all-below") == 0;
     if (!range_mode && !below_mode && !all_mode && argc != 4) {
         fprintf(stderr, "usage: %s MSG LOWER UPPER | --range MSG LOWER COUNT | --below MSG LOWER UPPER TARGET"
-                        " | --all-below MSG LOWER UPPER TARGET [CAP] | [--packed] --batch FILE | --batch-below FILE | [--packed] --batch-all-below FILE | --version\n", argv[0]);
+                        " | --all-below MSG LOWER UPPER TARGET [CAP] | [--packed] --batch FILE | [--early] --batch-below FILE | [--packed] --batch-all-below FILE | --version\n", argv[0]);
         return 2;
     }
     const int opt = range_mode || below_mode || all_mode;

@@ -304,8 +304,9 @@ struct Staged {
     }
 
     // A first-hit batch stage: as above, with target[k] job k's target.
-    Staged(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk)
-        : st(plans, target, rchunk), meta(st.bytes) {
+    Staged(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk,
+           const std::vector<const BatchJob*>* packed = nullptr)
+        : st(plans, target, rchunk, packed), meta(st.bytes) {
         read_groups();
     }
 
@@ -1207,6 +1208,174 @@ int hostcheck_stage_first_batch(const uint8_t* msgs, const uint64_t* msg_off, ui
         st.fill(meta);
     }
     return (int)st.groups.size();
+}
+
+}  // extern "C"
+
+// ---- early first-hit batch (gpuhash_first_below_batch_early): CPU replay of its rounds ----
+//
+// The rule, the rounds and their sub-batches as the engine cuts them (stage.h, early_limit and the
+// chunk rule; gpuhash.cpp, early_rounds), each round's stage from the bytes fill() wrote and
+// k_pack_first over its tiles through PackReplay: pack.h's own hashing, the orders and the stale
+// reads of the packed replay (a stale bound is the word as armed, all ones: every round is a stage
+// of its own).  A wave's run keeps the lanes at or below the bound it read -- a wave none of whose
+// lanes is has nothing to commit, which is the kernel's skip -- and its lowest hit lane does the
+// atomicMin and the bounded append.  The skip is modelled by its outcome only: the replay cannot
+// catch a fault in the branch itself (a skip that is not wave-uniform, or one placed before the
+// runs are computed); the GPU tests alone cover that branch.  The remainder goes through
+// hostcheck_first_below_batch.
+
+namespace {
+
+// One round's packed group over the stage's {bound, target} words.  Returns the appends in all,
+// kept or not.
+uint64_t pack_first_group(const Staged& staged, std::vector<uint64_t>& words, std::vector<BatchEntry>& list,
+                          uint64_t order_seed, Rng& rng) {
+    const PackReplay pk(staged);
+    uint32_t head[4];
+    std::memcpy(head, staged.meta.data() + staged.st.list_at, sizeof head);
+    const uint64_t cap = head[1];
+    uint64_t appended = 0;
+    pk.group(order_seed, rng,
+             [&](PackRun& r, bool stale) {
+                 r.seen = stale ? ~0ull : words[2 * (size_t)r.job];
+                 const uint64_t target = words[2 * (size_t)r.job + 1];
+                 // the run's lowest hit lane among those that needed their hash
+                 std::vector<PackLane> hit;
+                 for (const PackLane& l : r.lanes)
+                     if (l.n <= r.seen && l.h <= target) { hit.push_back(l); break; }
+                 r.lanes = hit;
+             },
+             [&](PackRun& r) {
+                 if (r.lanes.empty()) return;
+                 const PackLane& b = r.lanes[0];
+                 const uint64_t old = words[2 * (size_t)r.job];  // the atomicMin
+                 words[2 * (size_t)r.job] = std::min(old, b.n);
+                 if (b.n > old) return;  // equal only at 2^64-1 against the word as armed
+                 if (appended++ < cap) list.push_back(BatchEntry{b.h, b.n, r.job, 0});
+             });
+    return appended;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t hostcheck_early_limit(uint64_t lower, uint64_t upper, uint64_t target, uint64_t prefix) {
+    return early_limit(lower, upper, target, prefix);
+}
+
+uint64_t hostcheck_early_first_chunk(uint64_t fronts) { return early_first_chunk(fronts); }
+
+// gpuhash_first_below_batch_early as the engine runs it.  Returns what hostcheck_first_below_batch
+// returns, the per-job results as it gives them, in out_packed[k] the packed nonces handed out to
+// job k (the pieces of the rounds it was open in: what it hashed at most), and in out_fill[0..5]:
+// the largest result-list fill of any round's stage (appends the bounded store left out included),
+// that stage's capacity, how many stages filled their list past it, the number of round stages,
+// the remainder's stages over their bound, and c_0.
+int hostcheck_first_below_batch_early(const uint8_t* msgs, const uint64_t* msg_off, uint64_t njobs,
+                                      const uint64_t* lower, const uint64_t* upper, const uint64_t* target,
+                                      uint64_t prefix, uint32_t rchunk, int policy, uint64_t order_seed,
+                                      uint64_t batch_bytes, int nshards, uint64_t* out_hashes, uint64_t* out_nonces,
+                                      int* out_found, uint64_t* out_packed, uint64_t* out_fill) {
+    if (!msg_off || !lower || !upper || !target || !out_hashes || !out_nonces || !out_found || !out_packed ||
+        !out_fill || !njobs || nshards < 1 || prefix > GPUHASH_BATCH_MAX_SPAN)
+        return -1;
+    for (uint64_t k = 0; k < njobs; k++)
+        if (lower[k] > upper[k] || msg_off[k + 1] < msg_off[k] || upper[k] - lower[k] >= GPUHASH_BATCH_MAX_SPAN)
+            return -1;
+    Rng rng{order_seed};
+    uint64_t fill[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<uint64_t> limit(njobs), used(njobs, 0);
+    std::vector<size_t> fronts;
+    for (uint64_t k = 0; k < njobs; k++) {
+        out_found[k] = 0;
+        limit[k] = early_limit(lower[k], upper[k], target[k], prefix);
+        if (limit[k]) fronts.push_back((size_t)k);
+    }
+    std::vector<PackJob> recs(njobs);
+    for (size_t k : fronts) {
+        const uint64_t len = msg_off[k + 1] - msg_off[k];
+        recs[k] = PackTables::record(len ? msgs + msg_off[k] : nullptr, len);
+    }
+    const uint64_t c0 = fill[5] = early_first_chunk(fronts.size());
+    const size_t nruns = std::min<size_t>((size_t)nshards, fronts.size());
+    for (size_t r = 0; r < nruns; r++) {
+        const std::vector<size_t> mine(fronts.begin() + (long)(fronts.size() * r / nruns),
+                                       fronts.begin() + (long)(fronts.size() * (r + 1) / nruns));
+        for (uint64_t c = c0;; c = early_next_chunk(c)) {
+            std::vector<size_t> open;
+            std::vector<BatchJob> piece;
+            std::vector<uint64_t> tg;
+            for (size_t k : mine) {
+                if (out_found[k] || used[k] >= limit[k]) continue;
+                const uint64_t lo = lower[k] + used[k], len = msg_off[k + 1] - msg_off[k];
+                open.push_back(k);
+                piece.push_back(BatchJob{len ? msgs + msg_off[k] : nullptr, len, lo,
+                                         lo + (std::min(c, limit[k] - used[k]) - 1), &recs[k]});
+                tg.push_back(target[k]);
+            }
+            if (open.empty()) break;
+            auto plan = [&](size_t i) {
+                PlannedJob p = plan_packed_job(piece[i]);
+                p.bytes += 8;
+                return p;
+            };
+            auto run = [&](size_t first, std::vector<PlannedJob>& jobs) {
+                StageJobs sj(jobs, 0, jobs.size());
+                const Staged staged(sj.plans, tg.data() + first, rchunk, sj.which());
+                if (staged.st.groups.size() != 1 || staged.st.groups[0].C2 != 4) return -3;  // the packed group alone
+                std::vector<uint64_t> words(2 * jobs.size());
+                std::memcpy(words.data(), staged.meta.data() + staged.st.thresh_at, 16 * jobs.size());
+                std::vector<BatchEntry> list;
+                const uint64_t appended = pack_first_group(staged, words, list, order_seed, rng);
+                fill[3]++;
+                if (appended >= fill[0]) { fill[0] = appended; fill[1] = staged.st.list_cap; }
+                fill[2] += appended > staged.st.list_cap ? 1 : 0;
+                for (const BatchEntry& e : list) {  // the host's fold: the lowest nonce
+                    const size_t k = open[first + e.job];
+                    if (!out_found[k] || e.nonce < out_nonces[k]) { out_hashes[k] = e.hash; out_nonces[k] = e.nonce; }
+                    out_found[k] = 1;
+                }
+                return 0;
+            };
+            if (int rc = for_each_sub_batch(open.size(), batch_bytes_bound(batch_bytes), plan, run)) return rc;
+            for (size_t i = 0; i < open.size(); i++) used[open[i]] += piece[i].hi - piece[i].lo + 1;
+        }
+    }
+    for (uint64_t k = 0; k < njobs; k++) out_packed[k] = used[k];
+    // the remainder: the jobs still open, each with its own copy of its message
+    std::vector<size_t> sel;
+    std::vector<uint64_t> lo2, hi2, tg2, off2(1, 0);
+    std::vector<uint8_t> msgs2;
+    for (uint64_t k = 0; k < njobs; k++) {
+        if (out_found[k] || used[k] > upper[k] - lower[k]) continue;
+        sel.push_back((size_t)k);
+        lo2.push_back(lower[k] + used[k]);
+        hi2.push_back(upper[k]);
+        tg2.push_back(target[k]);
+        if (msg_off[k + 1] > msg_off[k]) msgs2.insert(msgs2.end(), msgs + msg_off[k], msgs + msg_off[k + 1]);
+        off2.push_back(msgs2.size());
+    }
+    int rc = 0;
+    if (!sel.empty()) {
+        const size_t n = sel.size();
+        std::vector<uint64_t> h2(n), n2(n), trace(3 * n), fill2(4);
+        std::vector<int> f2(n);
+        rc = hostcheck_first_below_batch(msgs2.data(), off2.data(), n, lo2.data(), hi2.data(), tg2.data(), rchunk, policy,
+                                         order_seed, batch_bytes, nshards, h2.data(), n2.data(), f2.data(), trace.data(),
+                                         fill2.data());
+        if (rc != 0 && rc != -2) return rc;
+        fill[4] = fill2[2];
+        for (size_t i = 0; i < n; i++) {
+            if (!f2[i]) continue;
+            out_found[sel[i]] = 1;
+            out_hashes[sel[i]] = h2[i];
+            out_nonces[sel[i]] = n2[i];
+        }
+    }
+    std::memcpy(out_fill, fill, sizeof fill);
+    return rc;
 }
 
 }  // extern "C"

@@ -81,4 +81,11 @@ struct PackArgs {
 unsigned int pack_grid_for(int mode, int device);
 hipError_t launch_pack(int mode, const PackArgs& a);
 
+// The packed group of a first-hit batch stage, a round of gpuhash_first_below_batch_early
+// (pack_first_kernel.hip, a code object of its own): one persistent launch of k_pack_first over
+// the group's tiles.  thresh, list and head are kScanFirstBatch's: {bound, target} per job, the
+// result list and its head.
+unsigned int pack_first_grid_for(int device);
+hipError_t launch_pack_first(const PackArgs& a);
+
 }  // namespace gpuhash

@@ -220,8 +220,9 @@ struct PackTables {
 
     bool empty() const { return recs.empty(); }
 
-    // Adds job `job` of the stage: msg of len bytes over [lo, hi], hi - lo < kPackMaxSpan.
-    void add_job(uint32_t job, const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi) {
+    // The record of a message: its midstate over the whole blocks and its tail.  (`job` is the
+    // stage's to set, add_job.)
+    static PackJob record(const uint8_t* msg, uint64_t len) {
         PackJob r{};
         std::copy(kIV, kIV + 8, r.cv);
         const uint64_t whole = len / 64, o = len % 64;
@@ -238,7 +239,20 @@ struct PackTables {
             r.tail[i >> 2] |= (uint32_t)c << (24 - 8 * (i & 3));
         }
         r.bits = 8 * (len + 1);
+        return r;
+    }
+
+    // Adds job `job` of the stage: msg of len bytes over [lo, hi], hi - lo < kPackMaxSpan.
+    void add_job(uint32_t job, const uint8_t* msg, uint64_t len, uint64_t lo, uint64_t hi) {
+        add_job(job, record(msg, len), lo, hi);
+    }
+
+    // The same from a record built before (record()): a caller that stages one job many times
+    // (the rounds of gpuhash_first_below_batch_early) compresses its whole blocks once.
+    void add_job(uint32_t job, const PackJob& built, uint64_t lo, uint64_t hi) {
+        PackJob r = built;
         r.job = job;
+        const uint32_t o = (uint32_t)(r.bits / 8 - 1) % 64;
         const uint32_t rec = (uint32_t)recs.size();
         recs.push_back(r);
         for (int d = num_digits(lo); d <= num_digits(hi); d++) {

@@ -85,6 +85,7 @@ struct StageTab {
 struct BatchJob {
     const uint8_t* msg;
     uint64_t len, lo, hi;
+    const PackJob* rec = nullptr;  // a packed job's record where the caller built it before (pack.h)
 };
 
 // the list's head: its append counter and its capacity in entries (a uint32 each), padding
@@ -169,6 +170,29 @@ struct PlannedJob {
 inline bool packs(int policy, uint64_t lo, uint64_t hi) {
     return (policy & GPUHASH_LAYOUT_PACKED_ALWAYS) && hi - lo < kPackMaxSpan;
 }
+
+// gpuhash_first_below_batch_early (include/gpuhash.h, where the rule is stated): how many leading
+// nonces of the job [lo, hi] with `target` run in packed rounds.  prefix != 0 forces min(span,
+// prefix); else 4 * E, E = ceil(2^64 / (target + 1)) = floor((2^64 - 1) / (target + 1)) + 1, while
+// that is at most GPUHASH_EARLY_MAX_PREFIX, and 0 beyond it.
+inline uint64_t early_limit(uint64_t lo, uint64_t hi, uint64_t target, uint64_t prefix) {
+    const uint64_t span = hi - lo + 1;  // <= GPUHASH_BATCH_MAX_SPAN
+    if (prefix) return std::min(span, prefix);
+    if (target == ~0ull) return std::min<uint64_t>(span, 4);
+    const uint64_t q = ~0ull / (target + 1);  // E - 1
+    if (q >= GPUHASH_EARLY_MAX_PREFIX / 4) return 0;
+    return std::min(span, 4 * (q + 1));
+}
+
+// The items a round of it gives every job at most: the first round's, for `fronts` jobs with a
+// packed front, and the next round's after one of c.
+constexpr uint64_t kEarlyRoundItems = 1ull << 20;  // <= kPackMaxSpan: a piece is one packed job
+inline uint64_t early_first_chunk(uint64_t fronts) {
+    uint64_t c = 64;
+    while (c < kEarlyRoundItems && c * fronts < kEarlyRoundItems) c *= 2;
+    return c;
+}
+inline uint64_t early_next_chunk(uint64_t c) { return std::min(2 * c, kEarlyRoundItems); }
 
 // A packed nonce against a nonce of a full row of the plain layouts (plan_cost's unit): it builds
 // its whole block and schedule itself.  Only the balance of a batch's runs over entries reads it.
@@ -336,7 +360,10 @@ struct Stage {
     }
 
     // The stage of a first-hit batch: plans[k] as above, target[k] job k's target.  See by_digits.
-    Stage(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk)
+    // packed: null, or per job the job itself where it runs packed: a round of
+    // gpuhash_first_below_batch_early, whose stage holds the packed group and nothing else.
+    Stage(std::vector<std::vector<Launch>>& plans, const uint64_t* target, uint32_t rchunk,
+          const std::vector<const BatchJob*>* packed = nullptr)
         : gmax(rchunk ? rchunk : kDefaultMaxPiece), gmin(std::min(kMinPiece, gmax)), njobs(plans.size()),
           by_digits(true), targets(target, target + plans.size()) {
         for (size_t k = 0; k < plans.size(); k++)
@@ -344,6 +371,7 @@ struct Stage {
                 l.desc.job = (uint32_t)k;
                 plan.push_back(std::move(l));
             }
+        if (packed) take_packed(*packed);
         lay_out();
     }
 
@@ -371,7 +399,10 @@ struct Stage {
    private:
     void take_packed(const std::vector<const BatchJob*>& packed) {
         for (size_t k = 0; k < packed.size(); k++)
-            if (const BatchJob* j = packed[k]) pack.add_job((uint32_t)k, j->msg, j->len, j->lo, j->hi);
+            if (const BatchJob* j = packed[k]) {
+                if (j->rec) pack.add_job((uint32_t)k, *j->rec, j->lo, j->hi);
+                else pack.add_job((uint32_t)k, j->msg, j->len, j->lo, j->hi);
+            }
         pack.finish();
     }
 

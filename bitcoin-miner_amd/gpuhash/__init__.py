@@ -48,6 +48,8 @@ LAYOUT_TAIL_ALWAYS, LAYOUT_TAIL_NEVER = 16, 32
 LAYOUT_PACKED_ALWAYS = 64  # min_batch and collect_below_batch: jobs of <= PACKED_MAX_SPAN nonces run packed
 PACKED_MAX_SPAN = 1 << 20
 TAIL_MIN_SPAN = 1 << 33
+# first_below_batch_early: the longest packed front its rule gives a job (GPUHASH_EARLY_MAX_PREFIX)
+EARLY_MAX_PREFIX = 1 << 24
 
 # Every symbol include/gpuhash.h declares (tests check the .so exports all of them).
 EXPORTED = [
@@ -57,7 +59,7 @@ EXPORTED = [
     "gpuhash_first_below", "gpuhash_first_below_ex",
     "gpuhash_collect_below", "gpuhash_collect_below_ex",
     "gpuhash_min_batch", "gpuhash_min_batch_ex",
-    "gpuhash_first_below_batch", "gpuhash_first_below_batch_ex",
+    "gpuhash_first_below_batch", "gpuhash_first_below_batch_ex", "gpuhash_first_below_batch_early",
     "gpuhash_collect_below_batch", "gpuhash_collect_below_batch_ex",
     "gpuhash_hash_range", "gpuhash_hash_cpu", "gpuhash_last_stats", "gpuhash_last_launches",
     "gpuhash_cancel", "gpuhash_resume", "gpuhash_progress",
@@ -186,6 +188,12 @@ def _lib(path: str | None = None) -> ctypes.CDLL:
                                                  ctypes.POINTER(u64), ctypes.POINTER(u64),
                                                  ctypes.POINTER(ctypes.c_int)]
     lib.gpuhash_first_below_batch_ex.restype = ctypes.c_int
+    if hasattr(lib, "gpuhash_first_below_batch_early"):  # an older build loaded by path has none
+        lib.gpuhash_first_below_batch_early.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
+                                                        ctypes.POINTER(u64), ctypes.POINTER(u64), u64,
+                                                        ctypes.c_uint32, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                        ctypes.POINTER(ctypes.c_int)]
+        lib.gpuhash_first_below_batch_early.restype = ctypes.c_int
     lib.gpuhash_collect_below_batch.argtypes = [vp, vp, ctypes.POINTER(sz), sz, ctypes.POINTER(u64),
                                                 ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(sz),
                                                 ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
@@ -362,6 +370,24 @@ class Engine:
                                                     rchunk, hashes, nonces, found)
         if rc != GPUHASH_OK:
             raise GpuHashError(rc, "gpuhash_first_below_batch")
+        return [(int(hashes[k]), int(nonces[k])) if found[k] else None for k in range(n)]
+
+    def first_below_batch_early(self, jobs, prefix: int = 0, rchunk: int = 0) -> list[tuple[int, int] | None]:
+        """first_below_batch for jobs whose first hit lies early in their range (stamp jobs): the
+        same results, with the first nonces of every job hashed packed, one (job, nonce) per GPU
+        lane, in ascending rounds of doubling pieces, and what is left of the jobs still open as
+        first_below_batch runs it (gpuhash_first_below_batch_early).  prefix = 0 lets every job's
+        target decide how many of its nonces run packed, at most EARLY_MAX_PREFIX; another value,
+        up to GPUHASH_BATCH_MAX_SPAN, forces it (tuning).  Jobs are checked as for
+        first_below_batch."""
+        n, data, off, lower, upper, target = self._batch_arrays(jobs, rchunk, 4)
+        if isinstance(prefix, bool) or not isinstance(prefix, int) or not 0 <= prefix <= GPUHASH_BATCH_MAX_SPAN:
+            raise ValueError(f"prefix={prefix!r} outside [0, GPUHASH_BATCH_MAX_SPAN]")
+        hashes, nonces, found = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)(), (ctypes.c_int * n)()
+        rc = self._lib.gpuhash_first_below_batch_early(self._ctx, ctypes.addressof(data), off, n, lower, upper,
+                                                       target, prefix, rchunk, hashes, nonces, found)
+        if rc != GPUHASH_OK:
+            raise GpuHashError(rc, "gpuhash_first_below_batch_early")
         return [(int(hashes[k]), int(nonces[k])) if found[k] else None for k in range(n)]
 
     def first_below(self, msg, lower: int, upper: int, target: int, rchunk: int = 0) -> tuple[int, int] | None:

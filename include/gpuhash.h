@@ -336,6 +336,45 @@ int gpuhash_first_below_batch_ex(gpuhash_ctx *ctx, const uint8_t *msgs, const si
                                  const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
                                  uint32_t rchunk, uint64_t *out_hashes, uint64_t *out_nonces, int *out_found);
 
+/* gpuhash_first_below_batch_ex for jobs whose first hit lies EARLY in their range (stamp jobs: a
+ * range of 2^32 nonces, an answer some 10^4-10^6 nonces in).  The results are exactly those of
+ * gpuhash_first_below_batch_ex on the same arguments -- the LOWEST qualifying nonce per job, under
+ * every layout policy, tail flag, rchunk, prefix and number of context entries; only speed differs.
+ * The front of every job runs PACKED, every lane hashing one (job, nonce) as under
+ * GPUHASH_LAYOUT_PACKED_ALWAYS (which this call ignores), in ascending rounds whose pieces double:
+ * round r gives every job still open the next min(c_r, what is left of its front) nonces, c_0 =
+ * 2^20 / (jobs with a front) rounded up to a power of two and clamped to [64, 2^20], c_(r+1) =
+ * min(2 c_r, 2^20).  One launch per round, per context entry, per sub-batch; a job with a hit in a
+ * round is answered by that round's lowest hit and closed.  A job whose answer lies x nonces above
+ * lower[k], inside its front, hashes at most 2x + c_0 packed nonces.  What is left of the jobs
+ * still open after their fronts runs as gpuhash_first_below_batch_ex runs it, with rchunk.
+ * The front of job k is its first limit_k nonces.  prefix != 0 forces limit_k = min(span_k, prefix)
+ * for every job (tuning and tests, as rchunk).  prefix == 0 is the rule, stated here ONCE
+ * (csrc/stage.h, early_limit, implements it): with E_k = ceil(2^64 / (target[k] + 1)), the expected
+ * position of the first hit,
+ *   4 * E_k <= GPUHASH_EARLY_MAX_PREFIX  -> limit_k = min(span_k, 4 * E_k)
+ *   otherwise                            -> limit_k = 0
+ * (a geometric first hit lies beyond 4 * E_k with probability e^-4).  So a job with target 0 goes
+ * straight to the scan path.  GPUHASH_EARLY_MAX_PREFIX is the largest power of two, up to 16 *
+ * GPUHASH_PACKED_MAX_SPAN, at which the packed front measured faster than
+ * gpuhash_first_below_batch (0.81 of its time at 2^24, 1.34 at 2^26).
+ * Whole-call argument errors: everything gpuhash_first_below_batch_ex refuses, and GPUHASH_EINVAL
+ * for prefix > GPUHASH_BATCH_MAX_SPAN; all detected before any use of ctx's contents and before
+ * anything is written to the outputs.  There is no _ex twin: rchunk is an argument.
+ * Afterwards gpuhash_last_stats().nonces is the ascending-scan figure of
+ * gpuhash_first_below_batch and .launches every launch that ran.  gpuhash_last_launches gives one
+ * record per round per sub-batch, the rounds of one context entry together and in order -- J = -1,
+ * C2 = 4, EX = 0, digits = 0, `c` the most tail blocks, `nonces` the round's items, `lo` and `hi`
+ * the lowest and the highest batch index among its jobs -- and then the remainder's records as
+ * gpuhash_first_below_batch writes them, with the same meaning of `lo` and `hi`.  gpuhash_cancel is
+ * read before every round and every sub-batch too, and gpuhash_progress counts the pieces handed
+ * out.  Replaces nothing in the reference. */
+#define GPUHASH_EARLY_MAX_PREFIX (1u << 24)
+int gpuhash_first_below_batch_early(gpuhash_ctx *ctx, const uint8_t *msgs, const size_t *msg_off, size_t njobs,
+                                    const uint64_t *lower, const uint64_t *upper, const uint64_t *target,
+                                    uint64_t prefix, uint32_t rchunk,
+                                    uint64_t *out_hashes, uint64_t *out_nonces, int *out_found);
+
 /* njobs independent gpuhash_collect_below collections in one call (a miner holding many short work
  * units, each with its own message, range and share target; a service counting hits per message
  * to calibrate a difficulty): out_totals[k] is exactly what gpuhash_collect_below(ctx, msg_k,
